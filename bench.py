@@ -14,7 +14,18 @@ RCCL unique id around); every collective of the measurement -- the barriers, the
 of the timed region, the all-gather of the C4 results -- is RCCL over xGMI driven by the C++
 library (picp_comm_*, include/picp_c.h).
 
-Sub-results on the same line (default run, bounded time):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set up,
+W warm-up steps, one timed region of exactly K steps, the outputs if --dump-outputs is given, the
+line.  Everything below that takes runs of its own -- the sub-results, the CPU baselines, the
+parity against the oracle, the streaming roofline, the with-convergence and keep-outliers legs,
+the median over 5 timed regions, the side file -- is behind --full.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path returned to its
+caller at its last step as DIR/<name>.npy (float32 / float64): the solved poses and the per-frame
+solve statistics (c2, c3, c4: every frame of the batch; c5: every step of this rank's segments).
+The inputs are seeded, so two builds run with the same arguments solve identical inputs.
+
+Sub-results on the same line (--full run, bounded time):
   c4 : BASELINE configs[3]: 1024 independent frames x 10k correspondences, sharded across the N
        GPUs (strong scaling of the fixed batch: each rank solves picp_shard_range's frames; the
        timed region ends with one RCCL all-gather of all 1024 poses + stats).
@@ -176,8 +187,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--n", type=int, default=0, help="override correspondences per frame")
     ap.add_argument("--problems", type=int, default=0, help="override frames (c4: total over ranks)")
-    ap.add_argument("--samples", type=int, default=5,
-                    help="timed regions of K steps each; value = the median (BASELINE.md: median of >= 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: sub-results (c3, c4, c5), CPU baselines, parity "
+                         "against the oracle, the streaming roofline, the median over 5 timed regions, the "
+                         "side file (a plain run times K steps once and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned at its last step as "
+                         "DIR/<name>.npy (rank 0)")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="timed regions of K steps each; value = the median (default: 1, so that --steps is the "
+                         "number of timed steps; with --full 5, BASELINE.md: median of >= 5)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (headline)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--skip-extras", action="store_true",
@@ -198,6 +217,11 @@ def main():
                     help="where rank 0 writes the full result (sample lists, bases, every sub-result); "
                          "default gpurun_out/bench_detail_<workload>_n<N>.json; '-' = nowhere")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed solves and the line, nothing that takes runs of its own
+        args.no_cpu = args.skip_extras = True
+        args.stream_n = 0
+    if args.samples is None:
+        args.samples = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -216,7 +240,7 @@ def main():
         else:
             out = bench_frame(args, rk, torch)
         if rk.rank == 0:
-            detail = write_detail(out, args, rk.world)
+            detail = write_detail(out, args, rk.world) if (args.full or args.detail) else None
             print(json.dumps(compact_line(out, detail, args.workload in ("c4", "c5")), separators=(",", ":")),
                   flush=True)
     finally:
@@ -347,6 +371,35 @@ def compact_line(out, detail, sub_fields=False):
         line["world_size_observed"] = out["ranks"].get("world_size_observed")
     line["detail"] = detail
     return line
+
+
+DUMP_LIMIT = 64 << 20  # bytes over all arrays of one --dump-outputs
+
+
+def dump_outputs(args, rk, arrays):
+    """--dump-outputs DIR: rank 0 writes the arrays the timed path handed its caller at its last
+    step as DIR/<name>.npy (float64 arrays stay float64, everything else goes to float32).  Called
+    right after the timed region, before any later leg solves again."""
+    if not args.dump_outputs or rk.rank != 0:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise ValueError("--dump-outputs: more than %d bytes of outputs" % DUMP_LIMIT)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
+def _stats_rows(stats):
+    """picp_stats of every frame as float64 rows: chi_in, chi_out, n_in, ok, rounds, converged,
+    n_projected (the counts are exact in float64)."""
+    import numpy as np
+    keys = ("chi_in", "chi_out", "n_in", "ok", "rounds", "converged", "n_projected")
+    return np.array([[s[k] for k in keys] for s in stats], np.float64).reshape(len(stats), len(keys))
 
 
 def _sync(torch):
@@ -491,6 +544,7 @@ def bench_frame(args, rk, torch):
     elapsed, (ev_ms, launch_us), el_all = _timed_samples(rk, torch, lambda: b.time(args.steps, **params),
                                                          args.samples)
     T_gpu = b.poses()[0]
+    dump_outputs(args, rk, {"poses": b.poses(), "stats": _stats_rows(b.stats())})
     err = rk.max([synth.se3_log_norm(T_gpu, T_gt[0])])[0]
 
     info = b.info()
@@ -571,6 +625,7 @@ def bench_frame(args, rk, torch):
         sub.warmup = 2
         sub.cpu_seconds = 3.0
         sub.n = sub.problems = sub.frames = sub.obs = 0
+        sub.dump_outputs = None
         out["c4"] = _compact(bench_c4(sub, rk, torch))
         if rk.world == 1:
             out["c4"]["per_rank"], out["c4"]["projection"] = _c4_projection(sub, rk, torch, out["c4"]["value"])
@@ -710,6 +765,8 @@ def bench_c4(args, rk, torch, shard=None):
         return r, b.poses()
 
     elapsed, ((ev_ms, launch_us), allT), el_all = _timed_samples(rk, torch, job, args.samples)
+    if not solo:  # every frame's pose as the job gathered it; this rank's frames' statistics
+        dump_outputs(args, rk, {"poses": allT, "stats": _stats_rows(b.stats())})
     err = max(synth.se3_log_norm(b.poses()[i], bt["T_gt"][i]) for i in range(f1 - f0))
     err = rk.max([err])[0]
     mine = np.array_equal(allT[f0:f1], b.poses())  # the gather put this rank's rows in place
@@ -901,6 +958,10 @@ def bench_vo(args, rk, torch, seg_len=None, shard=None, tag="c5"):
     # correctness of what was timed: drift vs gt, PICP work done
     P, Rr, vinfo = vo.poses(), vo.step_records(), vo.info()
     vo.close()
+    if tag == "c5" and shard is None:  # this rank's segments, one after the other: poses and step records
+        dump_outputs(args, rk, {"poses": np.concatenate(P), "steps": np.stack(
+            [np.concatenate([r[k] for r in Rr]) for k in ("n_corr", "n_in", "rounds", "n_new", "chi_in", "chi_out",
+                                                          "converged", "n_projected")], 1).astype(np.float64)})
     err, rounds, corr = 0.0, 0, 0
     for k, f0 in enumerate(my_first):
         for t in range(1, len(P[k])):

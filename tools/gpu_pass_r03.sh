@@ -16,7 +16,7 @@ timeout -k 10 400 python -u tools/concurrency_check.py > $O/concurrency_check.lo
 grep -v "amdgpu.ids" $O/concurrency_check.log
 timeout -k 10 400 python -u tools/vo_chains_check.py 2001 "PICP_VO_CHAINS=1,PICP_VO_OVERLAP=0" "PICP_VO_OVERLAP=1" "PICP_VO_CHAINS=2" "PICP_VO_OVERLAP=1,PICP_VO_CHAINS=2" > $O/vo_chains_check.log 2>&1 || { echo "vo chains check failed"; tail -20 $O/vo_chains_check.log; exit 1; }
 grep -v "amdgpu.ids" $O/vo_chains_check.log
-timeout -k 10 300 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
 tail -1 $O/bench_default.json | cut -c1-400
 if [ -n "$AB_C5" ]; then for rep in 1 2; do
   for S in "PICP_VO_CHAINS=1 PICP_VO_OVERLAP=0" "PICP_VO_CHAINS=2 PICP_VO_OVERLAP=1"; do

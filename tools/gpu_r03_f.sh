@@ -18,5 +18,5 @@ for rep in 1 2 3; do
     python3 -c "import json; d=json.loads(open('$O/c5_ab.json').read().strip().splitlines()[-1]); print('c5 $S', round(d['value']), d['unit'], d['ms_per_step'], d['timing']['values'])"
   done
 done
-timeout -k 10 400 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
 tail -1 $O/bench_default.json | cut -c1-300

@@ -12,7 +12,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; tail $OUT/smoke.log; exit 1; }
 cat $OUT/smoke.log
 for s in a b; do
-  timeout -k 10 600 python -u bench.py --detail $OUT/bench_detail_$s.json > $OUT/bench_default_$s.json 2> $OUT/bench_default_$s.err || { echo "bench failed"; tail -20 $OUT/bench_default_$s.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full --detail $OUT/bench_detail_$s.json > $OUT/bench_default_$s.json 2> $OUT/bench_default_$s.err || { echo "bench failed"; tail -20 $OUT/bench_default_$s.err; exit 1; }
   tail -c 2100 $OUT/bench_default_$s.json
 done
 OUT=$OUT bash tools/r05/gpu_prof_c5.sh

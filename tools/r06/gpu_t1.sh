@@ -13,7 +13,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log
 grep -E "^step |cond" $OUT/pytest_gpu.log | head -20
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; tail $OUT/smoke.log; exit 1; }
 timeout -k 10 300 python -u tools/r05/vo_dump.py $OUT/seg0_8e.npz || exit 1
-timeout -k 10 600 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench failed"; tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench failed"; tail -20 $OUT/bench_default.err; exit 1; }
 tail -c 2000 $OUT/bench_default.json
 : > $OUT/ab_tri.log
 for args in "" "--frames 1281" "--seg-len 1250 --steps 2 --warmup 1 --samples 1"; do for v in libpicp_amd_trijac libpicp_amd; do
