@@ -204,22 +204,6 @@ __device__ __forceinline__ int vo_gather_items(const VoArgs& a, int s, int t, fl
   return n;
 }
 
-// Issue priority of a block's waves by phase (on by default; -DPICP_BPRIO=0 for A/B): the round's
-// tail (the wave reduction, the combine and partner exchange, the one-wave solve) is a dependency
-// chain; when a second block shares the CU (split 4), its linearize would take the SIMDs' issue
-// slots ahead of it.  C4 at 128 frames, split 4: 20.4M -> 22.9M it/s; split 2 and the VO step
-// kernel within noise (profiles/r04/c4_128/, profiles/r04/pair2/).
-#ifndef PICP_BPRIO
-#define PICP_BPRIO 1
-#endif
-#if PICP_BPRIO
-#define BPRIO_TAIL() __builtin_amdgcn_s_setprio(3)
-#define BPRIO_LIN() __builtin_amdgcn_s_setprio(0)
-#else
-#define BPRIO_TAIL() ((void)0)
-#define BPRIO_LIN() ((void)0)
-#endif
-
 // MINW: waves per SIMD the register budget must allow (2: <= 256 VGPRs, one 512-thread block per
 // CU; 4: <= 128 VGPRs, two 512-thread blocks per CU -- split 4's layout)
 template <int NPT, int PH, int BS, typename VoT = NoVo, int MINW = 2>
@@ -342,7 +326,12 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
   float chi_prev = FLT_MAX;  // exec/icp_test.cpp:89
   for (int round = 1; !s_done; ++round) {
     BSTAMP(0);
-    BPRIO_LIN();
+    // Issue priority of a block's waves by phase, low for the linearize, high for the round's tail
+    // (the wave reduction, the combine and partner exchange, the one-wave solve: a dependency
+    // chain): when a second block shares the CU (split 4), its linearize would take the SIMDs'
+    // issue slots ahead of it.  C4 at 128 frames, split 4: 20.4M -> 22.9M it/s; split 2 and the VO
+    // step kernel within noise (profiles/r04/c4_128/, profiles/r04/pair2/).
+    __builtin_amdgcn_s_setprio(0);
     Pose T;
     T.r00 = s_pose[0]; T.r10 = s_pose[1]; T.r20 = s_pose[2];
     T.r01 = s_pose[3]; T.r11 = s_pose[4]; T.r21 = s_pose[5];
@@ -389,7 +378,7 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
       BSTAMP(1);
       acc_fold(a, v);
     }
-    BPRIO_TAIL();
+    __builtin_amdgcn_s_setprio(3);  // the tail
     const float wred = wave_reduce32(v, lane);
     const float wsum = wave_counts(wred, lane, (Cnt){nr.n_in + nd.n_in, nr.n_proj + nd.n_proj});
     if ((lane & 1) == 0) s_wave[lane >> 1][wave] = wsum;
@@ -469,15 +458,11 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
     }
     // the totals (and s_tmo) were written by lanes < 32 of wave 0, which also runs the solve:
     // a wave barrier orders them, the other waves wait at the block barrier after the solve
-#ifdef PICP_FINISH_SYNC
-    __syncthreads();
-#else
     __builtin_amdgcn_wave_barrier();
-#endif
     BSTAMP(4);
     if (wave == 0) {  // the wave finishes the round (every lane the same values, state in registers)
       RoundOut o;
-      finish_round_pose<PICP_FINISH_WAVE>(A, s_tot, round, pr, pt, chi_prev, o);
+      finish_round_pose(A, s_tot, round, pr, pt, chi_prev, o);
       if (s_tmo) o.done = 1;  // a partner wait timed out: stop (the host reports the error)
       if (lane == 0) {
 #pragma unroll

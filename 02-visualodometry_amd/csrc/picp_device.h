@@ -512,107 +512,6 @@ __device__ __forceinline__ void accumulate_pinhole2(const Pose& T, const Cam& C,
   acc2_normal<true, KEEP>(J0, J1, e0, e1, w, a);
 }
 
-// A pair of correspondences, pinhole K, into ONE accumulation slot: accumulate_pinhole2's math on
-// float2 (two independent dependency chains through the projection, the gate and the Jacobian:
-// the instruction-level parallelism the two-slot form buys), then item A's terms and item B's
-// terms added into the same sums in that order -- exactly accumulate_pinhole(A) followed by
-// accumulate_pinhole(B), so the sums are the one-slot form's bits.  A skipped item's J and e are
-// zeroed (exact zeros: fma(+-0, x, h) == h, the sums never being -0), as accumulate_pinhole's
-// zeroing path does.
-template <bool KEEP, int RCP = RCP_CHECK>
-__device__ __forceinline__ void accumulate_pinhole_p1(const Pose& T, const Cam& C, float thr, float inv_thr,
-                                                      f2 x, f2 y, f2 z, f2 u, f2 v, bool inA, bool inB, Acc& a,
-                                                      Cnt& n) {
-  f2 pc0, pc1, pc2, ph0, ph1, iz, e0, e1, chi;
-  bool validA, validB;
-  {
-#pragma clang fp contract(off)
-    pc0 = ((T.r00 * x + T.r01 * y) + T.r02 * z) + T.t0;  // src/camera.h:26
-    pc1 = ((T.r10 * x + T.r11 * y) + T.r12 * z) + T.t1;
-    pc2 = pair_depth(T, x, y, z);
-    ph0 = C.k00 * pc0 + C.k02 * pc2;  // src/camera.h:29 without the zero terms
-    ph1 = C.k11 * pc1 + C.k12 * pc2;
-    if (RCP == RCP_FAST || (RCP == RCP_CHECK && __all(rcp_safe(pc2.x) & rcp_safe(pc2.y)))) {
-      iz.x = rcp_rn(pc2.x);
-      iz.y = rcp_rn(pc2.y);
-    } else {
-      iz.x = 1.0f / pc2.x;
-      iz.y = 1.0f / pc2.y;
-    }
-    const f2 ix = ph0 * iz;
-    const f2 iy = ph1 * iz;
-    validA = inA & !(pc2.x <= 0.0f) & !((ix.x < 0.0f) | (ix.x > C.maxx) | (iy.x < 0.0f) | (iy.x > C.maxy));
-    validB = inB & !(pc2.y <= 0.0f) & !((ix.y < 0.0f) | (ix.y > C.maxx) | (iy.y < 0.0f) | (iy.y > C.maxy));
-    e0 = ix - u;
-    e1 = iy - v;
-    chi = e0 * e0 + e1 * e1;
-  }
-  const bool outA = chi.x > thr, outB = chi.y > thr;
-  const bool inlA = validA & !outA, inlB = validB & !outB;
-  const bool useA = inlA | (validA & KEEP), useB = inlB | (validB & KEEP);
-  f2 w = {1.0f, 1.0f};
-  if constexpr (KEEP) {
-    const f2 q = chi * inv_thr;
-    w = (f2){useA ? (inlA ? 1.0f : __builtin_amdgcn_rsqf(q.x)) : 0.0f,
-             useB ? (inlB ? 1.0f : __builtin_amdgcn_rsqf(q.y)) : 0.0f};
-  }
-  a.chi_in += inlA ? chi.x : 0.0f;  // item A, then item B: the one-slot order
-  a.chi_out += (validA & outA) ? chi.x : 0.0f;
-  a.chi_in += inlB ? chi.y : 0.0f;
-  a.chi_out += (validB & outB) ? chi.y : 0.0f;
-  cnt_add(n, inlA, validA);
-  cnt_add(n, inlB, validB);
-#define PICP_Z2(val) val = (f2){useA ? val.x : 0.0f, useB ? val.y : 0.0f}
-  PICP_Z2(iz); PICP_Z2(pc0); PICP_Z2(pc1); PICP_Z2(pc2); PICP_Z2(ph0); PICP_Z2(ph1); PICP_Z2(e0); PICP_Z2(e1);
-#undef PICP_Z2
-  f2 J0[6], J1[6];
-  {
-#pragma clang fp contract(off)
-    const f2 iz2 = iz * iz;  // src/picp_solver.cpp:45-52, the oracle's operation order
-    const f2 jp0 = -(ph0 * iz2), jp1 = -(ph1 * iz2);
-    const f2 a00 = iz * C.k00, a02 = iz * C.k02 + jp0;
-    const f2 a11 = iz * C.k11, a12 = iz * C.k12 + jp1;
-    const f2 zero = {0.0f, 0.0f};
-    J0[0] = a00; J0[1] = zero; J0[2] = a02;
-    J0[3] = a02 * pc1;
-    J0[4] = a00 * pc2 - a02 * pc0;
-    J0[5] = -(a00 * pc1);
-    J1[0] = zero; J1[1] = a11; J1[2] = a12;
-    J1[3] = -(a11 * pc2) + a12 * pc1;
-    J1[4] = -(a12 * pc0);
-    J1[5] = a11 * pc0;
-  }
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {  // item A's terms, then item B's (accumulate_pinhole's order)
-    float W0[6], W1[6], K0[6], K1[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      K0[i] = it ? J0[i].y : J0[i].x;
-      K1[i] = it ? J1[i].y : J1[i].x;
-      const float wi = it ? w.y : w.x;
-      W0[i] = KEEP ? wi * K0[i] : K0[i];
-      W1[i] = KEEP ? wi * K1[i] : K1[i];
-    }
-    const float f0 = it ? e0.y : e0.x, f1 = it ? e1.y : e1.x;
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-      for (int j = i; j < 6; ++j) {
-        float h = a.h[k];
-        if (i != 0 && j != 0) h = fmaf(W1[i], K1[j], h);  // J1[0] == 0
-        if (i != 1 && j != 1) h = fmaf(W0[i], K0[j], h);  // J0[1] == 0
-        a.h[k] = h;
-        ++k;
-      }
-      float bb = a.b[i];
-      if (i != 0) bb = fmaf(W1[i], f1, bb);
-      if (i != 1) bb = fmaf(W0[i], f0, bb);
-      a.b[i] = bb;
-    }
-  }
-}
-
 // A pair of correspondences, general K: per-item math (item_general), paired accumulation.
 __device__ __forceinline__ void accumulate_general2(const Pose& T, const Cam& C, float thr, bool keep,
                                                     f2 x, f2 y, f2 z, f2 u, f2 v, bool inA,
@@ -679,23 +578,9 @@ __device__ __forceinline__ void accumulate_regs(const Pose& T, const Cam& C, flo
 // Which accumulation form a kernel with NPT register-resident items per lane uses.  Measured on
 // MI355X with the unpacked build (profiles/r03/acc/): one slot is faster at small NPT (C5, NPT 4:
 // +2.7 %), the two-slot pair form at NPT 8 (C3 +5-9 %, C4 +17 %: its two independent
-// accumulation chains and its paired LDS/stream loops).  -DPICP_ACC_PAIRS / -DPICP_ACC_ONE force
-// one form for A/B builds.
-// One-slot accumulation with the per-item math in pairs (accumulate_pinhole_p1): the same bits
-// as item by item.  -DPICP_P1=0 restores the item-by-item form for A/B builds.
-#ifndef PICP_P1
-#define PICP_P1 0
-#endif
-
-__host__ __device__ constexpr bool acc_pairs(int npt) {
-#if defined(PICP_ACC_PAIRS)
-  return true;
-#elif defined(PICP_ACC_ONE)
-  return false;
-#else
-  return npt >= 8;
-#endif
-}
+// accumulation chains and its paired LDS/stream loops).  (One slot with the per-item math in
+// pairs gave the same bits and no gain: DESIGN.md Appendix A, "paired one-slot".)
+__host__ __device__ constexpr bool acc_pairs(int npt) { return npt >= 8; }
 
 // accumulate_regs with ONE accumulator slot, item by item (the default since the device code is
 // built without packed FP32, hipcc_nopk.sh): the pair form's two slots only paid for themselves
@@ -719,23 +604,6 @@ __device__ __forceinline__ void accumulate_regs1(const Pose& T, const Cam& C, fl
     auto run = [&](auto rcp) {
       constexpr bool KP = PH == PICP_V_PINHOLE_KEEP;
       constexpr int R = decltype(rcp)::value;
-#if PICP_P1
-      // items in pairs (k, k + 1) through accumulate_pinhole_p1: the same sums in the same order
-      // as item by item, with two dependency chains through the per-item math
-#pragma unroll
-      for (int k = 0; k + 1 < NPT; k += 2) {
-        const bool inA = first + k * stride < n, inB = first + (k + 1) * stride < n;
-        if (k + 2 < NPT || __any(inB))  // the last slot only in waves that hold an item there
-          accumulate_pinhole_p1<KP, R>(T, C, thr, inv_thr, (f2){xs[k], xs[k + 1]}, (f2){ys[k], ys[k + 1]},
-                                       (f2){zs[k], zs[k + 1]}, (f2){us[k], us[k + 1]}, (f2){vs[k], vs[k + 1]}, inA,
-                                       inB, a, cnt);
-        else
-          accumulate_pinhole<KP, R>(T, C, thr, inv_thr, xs[k], ys[k], zs[k], us[k], vs[k], inA, a, cnt);
-      }
-      if constexpr (NPT & 1)
-        accumulate_pinhole<KP, R>(T, C, thr, inv_thr, xs[NPT - 1], ys[NPT - 1], zs[NPT - 1], us[NPT - 1],
-                                  vs[NPT - 1], first + (NPT - 1) * stride < n, a, cnt);
-#else
 #pragma unroll
       for (int k = 0; k < NPT; ++k)
         // the last slot only in waves that hold an item there (a wave-uniform branch): a frame
@@ -745,7 +613,6 @@ __device__ __forceinline__ void accumulate_regs1(const Pose& T, const Cam& C, fl
         if (NPT < 2 || k + 1 < NPT || __any(first + k * stride < n))
           accumulate_pinhole<KP, R>(T, C, thr, inv_thr, xs[k], ys[k], zs[k], us[k], vs[k], first + k * stride < n, a,
                                     cnt);
-#endif
     };
     if (__all(fast))
       run(std::integral_constant<int, RCP_FAST>());
@@ -771,29 +638,10 @@ __device__ __forceinline__ void accumulate_item(const Pose& T, const Cam& C, flo
 }
 
 // Streamed (LDS or HBM) items i, i + stride, i + 2 stride, ... (i = first) of one lane into one
-// slot, in that order: pairs through accumulate_pinhole_p1 (the fast reciprocal by a vote of the
-// lanes that run the pair), the general variant item by item.  get(i, x, y, z, u, v) loads item i.
+// slot, in that order, item by item (accumulate_item).  get(i, x, y, z, u, v) loads item i.
 template <int PH, typename Get>
 __device__ __forceinline__ void accumulate_stream1(const Pose& T, const Cam& C, float thr, float inv_thr, bool keep,
                                                    int first, int stride, int count, Get get, Acc& a, Cnt& n) {
-#if PICP_P1
-  if constexpr (PH != PICP_V_GENERAL) {
-    constexpr bool KP = PH == PICP_V_PINHOLE_KEEP;
-    for (int i = first; i < count; i += 2 * stride) {
-      const bool inB = i + stride < count;
-      const int j = inB ? i + stride : i;
-      float x0, y0, z0, u0, v0, x1, y1, z1, u1, v1;
-      get(i, x0, y0, z0, u0, v0);
-      get(j, x1, y1, z1, u1, v1);
-      const f2 x = {x0, x1}, y = {y0, y1}, z = {z0, z1};
-      if (__all(pair_rcp_safe(T, x, y, z)))
-        accumulate_pinhole_p1<KP, RCP_FAST>(T, C, thr, inv_thr, x, y, z, (f2){u0, u1}, (f2){v0, v1}, true, inB, a, n);
-      else
-        accumulate_pinhole_p1<KP, RCP_DIV>(T, C, thr, inv_thr, x, y, z, (f2){u0, u1}, (f2){v0, v1}, true, inB, a, n);
-    }
-    return;
-  }
-#endif
   for (int i = first; i < count; i += stride) {
     float x, y, z, u, v;
     get(i, x, y, z, u, v);
@@ -911,23 +759,6 @@ __device__ __forceinline__ float wave_reduce32_bperm(float* v, int lane) {
 }
 
 __device__ __forceinline__ float wave_reduce32(float* v, int lane) {
-#ifdef PICP_NO_PERMLANE_SWAP
-  // the half-wave exchanges through ds_bpermute (bit-identical sums in the same order).  Results
-  // of the v_permlane*_swap form below moved in the last bits when other kernels ran beside it on
-  // MI355X; this form did not.  Costs C2 3 %, C4 15 %, C5 10 %.
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const bool hi = (lane & 32) != 0;
-    const float send = hi ? v[i] : v[i + 16], keep = hi ? v[i + 16] : v[i];
-    v[i] = keep + __shfl_xor(send, 32);
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bool hi = (lane & 16) != 0;
-    const float send = hi ? v[i] : v[i + 8], keep = hi ? v[i + 8] : v[i];
-    v[i] = keep + __shfl_xor(send, 16);
-  }
-#else
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 16]), false, false);
@@ -938,7 +769,6 @@ __device__ __forceinline__ float wave_reduce32(float* v, int lane) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 8]), false, false);
     v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   }
-#endif
   bfly_dpp<DPP_ROW_MIRROR, 3, 4>(v, lane);
   bfly_dpp<DPP_ROW_HALF_MIRROR, 2, 2>(v, lane);
   bfly_dpp<DPP_QUAD_XOR2, 1, 1>(v, lane);
@@ -1008,78 +838,6 @@ __device__ __forceinline__ bool ldl6_solve(const float* tw, float dx[6]) {
 
 __device__ __forceinline__ void ldl6_solve(const float* tw, float dx[6]) {
   if (ldl6_solve<false>(tw, dx)) ldl6_solve<true>(tw, dx);  // a (near-)zero pivot: rare
-}
-
-// DPP row_newbcast:N (gfx950): lane N of each 16-lane row, to every lane of that row.  bound_ctrl
-// set: a lane whose source is invalid would get 0, never a stale register (no source is invalid
-// here: every lane of a finishing wave is active), and no tied "old" copy is needed.
-template <int N>
-__device__ __forceinline__ float row_bcast(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + N, 0xF, 0xF, true));
-}
-
-// ldl6_solve with the elimination spread over the lanes of each 16-lane row: lane r (< 6) holds
-// row r of the lower triangle (its entries right of the diagonal are never read), and step j's
-// pivot, its rhs and column j (a[c][j], c > j) reach every lane by row_newbcast.  The same
-// operations on the same operands in the same order as ldl6_solve -- a[i][c] -= f_i a[c][j],
-// f_i = a[i][j] / d_j, rhs_i -= f_i rhs_j, the back substitution from the column values each step
-// broadcast -- so the result is bit-identical; 27 DPP moves replace 15 of the 35 trailing-update
-// FMAs' serial issue and the 21 loads of the one-lane form.  Every lane of the wave must be
-// active; every lane returns the same dx (each row solves the system).
-template <bool GUARD>
-__device__ __forceinline__ bool ldl6_solve_wave(const float* tw, float dx[6]) {
-  const int r0 = (int)(__lane_id() & 15);
-  const int r = r0 < 6 ? r0 : 5;  // lanes 6-15 shadow row 5 (never broadcast from)
-  float col[6];
-#pragma unroll
-  for (int c = 0; c < 6; ++c) col[c] = tw[tri_index(c, r)];
-  float rhs = tw[PICP_P_B + r];
-  float id[6], rj[6], lc[6][6];
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    float d, bj;
-    switch (j) {  // DPP controls are immediates
-      case 0: d = row_bcast<0>(col[0]); bj = row_bcast<0>(rhs); break;
-      case 1: d = row_bcast<1>(col[1]); bj = row_bcast<1>(rhs); break;
-      case 2: d = row_bcast<2>(col[2]); bj = row_bcast<2>(rhs); break;
-      case 3: d = row_bcast<3>(col[3]); bj = row_bcast<3>(rhs); break;
-      case 4: d = row_bcast<4>(col[4]); bj = row_bcast<4>(rhs); break;
-      default: d = row_bcast<5>(col[5]); bj = row_bcast<5>(rhs); break;
-    }
-    float inv = __builtin_amdgcn_rcpf(d);
-    if (GUARD) inv = (fabsf(d) > FLT_MIN) ? inv : 0.0f;
-    else bad |= !(fabsf(d) > FLT_MIN);
-    id[j] = inv;
-    rj[j] = bj;
-    const float f = col[j] * inv;
-#pragma unroll
-    for (int c = j + 1; c < 6; ++c) {
-      float b;
-      switch (c) {
-        case 1: b = row_bcast<1>(col[j]); break;
-        case 2: b = row_bcast<2>(col[j]); break;
-        case 3: b = row_bcast<3>(col[j]); break;
-        case 4: b = row_bcast<4>(col[j]); break;
-        default: b = row_bcast<5>(col[j]); break;
-      }
-      lc[c][j] = b;  // a[c][j] after steps < j: the back substitution's U[j][c]
-      col[c] = fmaf(-f, b, col[c]);
-    }
-    rhs = fmaf(-f, bj, rhs);
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; --k) {
-    const float x = rj[k] * id[k];
-    dx[k] = x;
-#pragma unroll
-    for (int i = 0; i < k; ++i) rj[i] = fmaf(-lc[k][i], x, rj[i]);
-  }
-  return bad;
-}
-
-__device__ __forceinline__ void ldl6_solve_wave(const float* tw, float dx[6]) {
-  if (ldl6_solve_wave<false>(tw, dx)) ldl6_solve_wave<true>(tw, dx);
 }
 
 // sin/cos of GN increment angles.  Increments are small, so the float Taylor series (exact to
@@ -1169,10 +927,8 @@ struct RoundOut {
 // min-inlier check, the 6x6 solve, the update and the icp_test loop rule.  The loop state a round
 // reads -- the pose R (column-major) / t and chi_prev -- is carried in registers by the finishing
 // wave (every lane computes the same values; no LDS state round trip on the critical path).
-// tw may be LDS.
-// WAVE: the caller is a whole wave with every lane active (the block and persistent kernels'
-// finishing wave): the elimination runs over each 16-lane row (ldl6_solve_wave, bit-identical).
-template <bool WAVE = false>
+// tw may be LDS.  (The elimination spread over a 16-lane row of the finishing wave was not
+// faster: DESIGN.md Appendix A, "DPP-row solve".)
 __device__ __forceinline__ void finish_round_pose(const PicpArgs& A, const float* tw, int j, float R[9],
                                                   float t[3], float& chi_prev, RoundOut& o) {
   o.chi_in = tw[PICP_P_CHI_IN];
@@ -1186,10 +942,7 @@ __device__ __forceinline__ void finish_round_pose(const PicpArgs& A, const float
     return;
   }
   float dx[6];
-  if constexpr (WAVE)
-    ldl6_solve_wave(tw, dx);  // :96 (damping folded in by total_word), :102
-  else
-    ldl6_solve(tw, dx);
+  ldl6_solve(tw, dx);  // :96 (damping folded in by total_word), :102
   apply_update(dx, R, t);  // :103
   o.ok = 1;
   o.done = 0;
@@ -1328,18 +1081,8 @@ __device__ __forceinline__ void tri_null_jacobi(double A[4][4], double v[4]) {
 // Two-view linear (DLT) triangulation of one point, cv::triangulatePoints as called from
 // src/cam.cpp:115 then convertPointsFromHomogeneous :118.  P1, P2: 3x4 ROW-major float.
 // A (4x4) in double; X_h = the right singular vector of A's smallest singular value, by the
-// one-sided Jacobi above (tri_null_jacobi).
-// -DPICP_TRI_INVIT (A/B, measured slower, not the default): the eigenvector of the smallest
-// eigenvalue of M = A^T A by inverse iteration on M through its
-// LDL^T (no pivoting: M is positive semi-definite and, for a finite point, its null direction has
-// w != 0, so the near-zero pivot is the last): x1 = M^-1 e4 (back substitution alone), then
-// x2 = M^-1 x1.  x2 is accepted when it moved less than ~1.4e-6 rad from x1 (1 - |cos| < 1e-12):
-// the error left after the second step is then below ~1e-12, the SVD's own rounding level.  A
-// point whose system is not that well separated (near-parallel rays, a point at infinity, a
-// degenerate ray pair, |w| <= 1e-5) takes the Jacobi SVD.  On the VO sequence's pairs (sigma4 / sigma3 ~1e-7)
-// every point takes the fast path, within 2.1e-11 of numpy's SVD.  Parity green (the long-segment
-// rule included), but the append got slower, not faster: C5 805k -> 777k frames/s, the N = 8
-// per-rank shape 161.4k -> 159.2k, 8e 42.7k -> 42.0k (profiles/r06/t1/ab_tri.log).
+// one-sided Jacobi above (tri_null_jacobi).  (Inverse iteration on A^T A was slower: DESIGN.md
+// Appendix A, "inverse-iteration triangulation".)
 __device__ inline void triangulate_dlt(const float* P1, const float* P2, float2 a, float2 b,
                                        float out[3]) {
   double A[4][4];
@@ -1351,44 +1094,7 @@ __device__ inline void triangulate_dlt(const float* P1, const float* P2, float2 
     A[3][k] = (double)b.y * (double)P2[8 + k] - (double)P2[4 + k];
   }
   double v[4];
-#ifndef PICP_TRI_INVIT
   tri_null_jacobi(A, v);
-#else
-  {
-    double M[4][4];  // upper triangle used
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = i; j < 4; ++j) M[i][j] = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j] + A[3][i] * A[3][j];
-    const double r0 = tri_rcp(M[0][0]);
-    const double l10 = M[0][1] * r0, l20 = M[0][2] * r0, l30 = M[0][3] * r0;
-    const double d1 = M[1][1] - l10 * M[0][1];
-    const double r1 = tri_rcp(d1);
-    const double l21 = (M[1][2] - l20 * M[0][1]) * r1, l31 = (M[1][3] - l30 * M[0][1]) * r1;
-    const double d2 = M[2][2] - l20 * M[0][2] - l21 * l21 * d1;
-    const double r2 = tri_rcp(d2);
-    const double l32 = (M[2][3] - l30 * M[0][2] - l31 * l21 * d1) * r2;
-    double d3 = M[3][3] - l30 * M[0][3] - l31 * l31 * d1 - l32 * l32 * d2;
-    d3 = (fabs(d3) > 1e-300) ? d3 : 1e-300;  // an exactly singular M: any tiny pivot gives its null vector
-    const double r3 = tri_rcp(d3);
-    // x1 = M^-1 e4 = L^-T (e4 / d3), normalised
-    double x3 = r3, x2 = -l32 * x3, x1 = -l21 * x2 - l31 * x3, x0 = -l10 * x1 - l20 * x2 - l30 * x3;
-    double s = tri_rsq(x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3);
-    x0 *= s; x1 *= s; x2 *= s; x3 *= s;
-    // x2' = M^-1 x1: forward L y = x1, then L^T x = y / d
-    const double y0 = x0, y1 = x1 - l10 * y0, y2 = x2 - l20 * y0 - l21 * y1,
-                 y3 = x3 - l30 * y0 - l31 * y1 - l32 * y2;
-    const double z3 = y3 * r3, z2 = y2 * r2 - l32 * z3, z1 = y1 * r1 - l21 * z2 - l31 * z3,
-                 z0 = y0 * r0 - l10 * z1 - l20 * z2 - l30 * z3;
-    s = tri_rsq(z0 * z0 + z1 * z1 + z2 * z2 + z3 * z3);
-    v[0] = z0 * s; v[1] = z1 * s; v[2] = z2 * s; v[3] = z3 * s;
-    const double c = fabs(v[0] * x0 + v[1] * x1 + v[2] * x2 + v[3] * x3);
-    // (|w| well above FLT_EPSILON: the dehomogenisation below is then sign-independent)
-    const bool ok = (c > 1.0 - 1e-12) && (c <= 1.0 + 1e-12) && (d1 > 0.0) && (d2 > 0.0) && (M[0][0] > 0.0) &&
-                    (fabs(v[3]) > 1e-5);
-    if (!ok) tri_null_jacobi(A, v);  // rare: the fallback runs with the lanes that need it
-  }
-#endif
   // points4D is float; convertPointsFromHomogeneous in float, scale 1 when |w| <= FLT_EPSILON
   const float X4 = (float)v[0], Y4 = (float)v[1], Z4 = (float)v[2], W4 = (float)v[3];
   const float scale = (fabsf(W4) > FLT_EPSILON) ? 1.0f / W4 : 1.0f;

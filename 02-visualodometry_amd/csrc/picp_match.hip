@@ -148,9 +148,7 @@ extern "C" hipError_t picp_launch_match(hipStream_t stream, int n_problems, int6
 typedef _Float16 mm_half8 __attribute__((ext_vector_type(8)));
 typedef float mm_f16v __attribute__((ext_vector_type(16)));
 
-#ifndef MM_WAVES
 #define MM_WAVES 4
-#endif
 #define MM_BLOCK (64 * MM_WAVES)
 // RB (kernel template argument): 32-query MFMA row blocks per wave, sharing every B operand.
 // The launcher takes RB = 2 when that still fills a generation of blocks (C5: +3.4 %,
@@ -242,31 +240,12 @@ extern "C" __global__ void picp_match_prep_kernel(const float* __restrict__ desc
 // are loaded clamped and masked in registers (norm := +inf).  LDS-DMA (global_load_lds) staging
 // was measured 30-40 % slower at full occupancy (C5, 4 blocks per CU: other blocks already hide
 // the fetch latency; profiles/r01/match_ab.log).
-#ifndef MM_RT
 #define MM_RT 256  // reference rows per LDS tile (128: -3.4 % on C5, 512: -7 %; profiles/r01/match_ab.log)
-#endif
-#ifndef MM_PF
-#define MM_PF 1  // tiles of references in flight ahead of the computed one (pass 2): 1, 2 or 3
-#endif
-static_assert(MM_PF >= 1 && MM_PF <= 3, "MM_PF: 1, 2 or 3");
-#ifndef MM_MERGE32
-#define MM_MERGE32 0  // 1: splits of 17-32 ranges merged in one 32-range chunk (A/B: 8e equal or
-                      // slower than two 16-range chunks, profiles/r06/t37/ab.log)
-#endif
-#ifndef MM_EARLY
-#define MM_EARLY 0  // 1: the next tile's fetch issued at the previous step's end (PF = 1; A/B:
-                    // equal at every C5 shape, profiles/r06/t35/ab.log)
-#endif
-static_assert(!MM_EARLY || MM_PF == 1, "MM_EARLY needs MM_PF = 1");
-#ifndef MM_PIPE_RB2
-#define MM_PIPE_RB2 1  // 0: the RB = 2 folded loop unpipelined (A/B)
-#endif
-#ifndef MM_BT
-#define MM_BT 4  // folded pass: column blocks whose B operands are read per LDS wait (RB = 1)
-#endif
-#ifndef MM_BT2
+// One tile of references is in flight ahead of the computed one (pass 2); more tiles ahead, an
+// earlier fetch, a 32-range merge chunk and the unpipelined RB = 2 loop were all measured equal or
+// slower ("prefetch depth", "early fetch", "32-range merge", "unpipelined RB 2").
+#define MM_BT 4   // folded pass: column blocks whose B operands are read per LDS wait (RB = 1)
 #define MM_BT2 4  // the same for RB = 2
-#endif
 // Diagnostic build only (-DPICP_STAMPS): [0] queries through the full-scan fallback, [1] total
 // candidates rescanned, [2] queries, [3] max candidates of a query (tools/match_stats.py).
 // Diagnostic build only (-DMM_TSTAMP): s_memtime phase sums of the folded pass-2 tile loop, lane 0
@@ -368,11 +347,8 @@ __device__ __forceinline__ unsigned mm_pack16(unsigned m) {
 // reference is a candidate iff S' >= 0; a 32x32 block with no candidate costs one max3 tree and
 // one wave vote instead of 48 VALU.  Tiles holding a reference outside the fold's range
 // (|r|^2 > 60000, unsafe) or past the end take the RAD = 1 compare.
-#ifndef MM_MINB
-#define MM_MINB 1
-#endif
 template <int KCH, int RAD, int RB>
-__global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
+__global__ __launch_bounds__(MM_BLOCK) void picp_match_mfma_kernel(
     const float* __restrict__ q_desc, const float* __restrict__ r_desc,
     const _Float16* __restrict__ q_h, const float* __restrict__ q_n1,
     const _Float16* __restrict__ r_h, const float* __restrict__ r_n1, const float* __restrict__ r_n2,
@@ -383,7 +359,7 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
   constexpr int QPW = 32 * RB;                      // queries per wave
   constexpr int QPB = MM_WAVES * QPW;               // queries per block
   constexpr int BT = (RB == 2) ? MM_BT2 : MM_BT;
-  constexpr bool PIPE = MM_PIPE_RB2 && RB == 2;  // the folded loop software-pipelined (below)
+  constexpr bool PIPE = RB == 2;                    // the folded loop software-pipelined (below)
   constexpr int DP = 16 * KCH;                      // halves per prepped row
   constexpr int CH = MM_RT * DP / 8;                // 16-B chunks per tile
   constexpr int CPT = CH / MM_BLOCK;                // 16-B chunks per thread per tile
@@ -465,10 +441,9 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
   const int64_t nr_all = P.nr;
   // fetch tile t0 into registers (chunk tid + k*MM_BLOCK; norm tid + k*MM_BLOCK of the tile's
   // [n1 | n2] block), stash them into buffer b
-  // the stage registers: MM_PF tiles in flight while tile t is computed (t + 1 .. t + MM_PF), in
-  // MM_PF stages whose roles rotate from tile to tile (no register moves)
-  mm_half8 stg[CPT], stg2[CPT], stg3[CPT];
-  float sn[NPN], sn2[NPN], sn3[NPN];
+  // the stage registers: tile t + 1 in flight while tile t is computed
+  mm_half8 stg[CPT];
+  float sn[NPN];
   auto fetch_to = [&](int64_t t0, mm_half8 (&g)[CPT], float (&gn)[NPN]) {
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -671,6 +646,8 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
   };
   // One tile: fold vote (RAD = 2) and barrier, the next tile's fetch into stage fs, the compute
   // on LDS buffer b, then the stage rs (the same registers: the fetch has landed) into b ^ 1.
+  // (fs / rs stay arguments although both are stg: naming stg in the body gives the same
+  // arithmetic in another register order, and this kernel's code is pinned to what was measured.)
 #ifdef MM_TSTAMP
   unsigned long long ts_acc[6] = {0, 0, 0, 0, 0, 0}, ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsl0 = 0, tsl1 = 0;
 #endif
@@ -683,7 +660,7 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
     if constexpr (RAD == 2) fold = lds.nofold[b] != (int)(t0 / MM_RT) + 1;
     MM_TS(ts1);
     const bool more = t0 + MM_RT < nr_all;
-    if (!MM_EARLY && t0 + MM_PF * MM_RT < nr_all) fetch_to(t0 + MM_PF * MM_RT, fs, fn);
+    if (t0 + MM_RT < nr_all) fetch_to(t0 + MM_RT, fs, fn);
     MM_TS(ts2);
     if (RAD == 2 && fold) {
       // folded radius test: element i of the accumulator is S' of (row i, column col)
@@ -755,9 +732,6 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
       if (more) {
         if (fold_check_of(rn)) lds.nofold[buf ^ 1] = (int)(t0 / MM_RT) + 2;  // the fetch has landed by now
         stash_from(buf ^ 1, t0 + MM_RT, rs, rn);
-        // MM_EARLY: the tile after next into the stage just freed, before this step's end (and the
-        // next step's barrier) rather than after that barrier
-        if (MM_EARLY && t0 + 2 * MM_RT < nr_all) fetch_to(t0 + 2 * MM_RT, fs, fn);
       }
 #ifdef MM_TSTAMP
       __builtin_amdgcn_s_waitcnt(0);  // the stash issued and landed
@@ -794,7 +768,6 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
       if constexpr (RAD == 2)
         if (fold_check_of(rn)) lds.nofold[buf ^ 1] = (int)(t0 / MM_RT) + 2;
       stash_from(buf ^ 1, t0 + MM_RT, rs, rn);
-      if (MM_EARLY && t0 + 2 * MM_RT < nr_all) fetch_to(t0 + 2 * MM_RT, fs, fn);
     }
   };
   if (nr_all > 0) {  // an empty reference set (a late part with no new points): no tile
@@ -804,29 +777,9 @@ __global__ __launch_bounds__(MM_BLOCK, MM_MINB) void picp_match_mfma_kernel(
       if (fold_check(0)) lds.nofold[0] = 1;
     }
     stash(0, 0);
-    if (MM_EARLY && MM_RT < nr_all) fetch(MM_RT);
   }
   MM_TS(tsl0);
-  if constexpr (MM_PF == 1) {
-    for (int64_t t0 = 0, b = 0; t0 < nr_all; t0 += MM_RT, b ^= 1) tile_step(t0, (int)b, stg, sn, stg, sn);
-  } else if constexpr (MM_PF == 2) {
-    if (MM_RT < nr_all) fetch_to(MM_RT, stg, sn);  // tile 1 in flight
-    for (int64_t t0 = 0; t0 < nr_all; t0 += 2 * MM_RT) {
-      tile_step(t0, 0, stg2, sn2, stg, sn);
-      if (t0 + MM_RT >= nr_all) break;
-      tile_step(t0 + MM_RT, 1, stg, sn, stg2, sn2);
-    }
-  } else {
-    if (MM_RT < nr_all) fetch_to(MM_RT, stg, sn);  // tiles 1 and 2 in flight
-    if (2 * MM_RT < nr_all) fetch_to(2 * MM_RT, stg2, sn2);
-    for (int64_t t0 = 0, b = 0; t0 < nr_all; t0 += 3 * MM_RT, b ^= 1) {
-      tile_step(t0, (int)b, stg3, sn3, stg, sn);
-      if (t0 + MM_RT >= nr_all) break;
-      tile_step(t0 + MM_RT, (int)b ^ 1, stg, sn, stg2, sn2);
-      if (t0 + 2 * MM_RT >= nr_all) break;
-      tile_step(t0 + 2 * MM_RT, (int)b, stg2, sn2, stg3, sn3);
-    }
-  }
+  for (int64_t t0 = 0, b = 0; t0 < nr_all; t0 += MM_RT, b ^= 1) tile_step(t0, (int)b, stg, sn, stg, sn);
 #ifdef MM_TSTAMP
   MM_TS(tsl1);
   ts_acc[5] = tsl1 - tsl0;
@@ -1012,16 +965,14 @@ static hipError_t mm_merge(hipStream_t stream, const MatchProblem* probs, int n_
                            int extra, const float4* part, float dist_thr, float ratio_thr, int32_t* best_idx,
                            float* best_dist, float* second_dist, int32_t* accepted) {
   const dim3 mg((unsigned)((max_nq + 255) / 256), (unsigned)n_problems);
-  // (MM_MERGE32: the ranges in one chunk wherever they fit 32 -- measured no faster)
+  // (17-32 ranges in one 32-range chunk measured no faster than two 16-range chunks: DESIGN.md
+  // Appendix A, "32-range merge")
   const int nr = ksplit + (extra >= 0 ? 1 : 0);
   if (nr <= 4)
     hipLaunchKernelGGL(picp_match_merge_kernel<4>, mg, dim3(256), 0, stream, probs, n_problems, ksplit, part, max_nq,
                        dist_thr, ratio_thr, best_idx, best_dist, second_dist, accepted, extra);
-  else if (nr <= 16 || MM_MERGE32 == 0)
-    hipLaunchKernelGGL(picp_match_merge_kernel<16>, mg, dim3(256), 0, stream, probs, n_problems, ksplit, part, max_nq,
-                       dist_thr, ratio_thr, best_idx, best_dist, second_dist, accepted, extra);
   else
-    hipLaunchKernelGGL(picp_match_merge_kernel<32>, mg, dim3(256), 0, stream, probs, n_problems, ksplit, part, max_nq,
+    hipLaunchKernelGGL(picp_match_merge_kernel<16>, mg, dim3(256), 0, stream, probs, n_problems, ksplit, part, max_nq,
                        dist_thr, ratio_thr, best_idx, best_dist, second_dist, accepted, extra);
   return hipGetLastError();
 }

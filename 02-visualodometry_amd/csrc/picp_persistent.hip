@@ -29,42 +29,23 @@ typedef __attribute__((address_space(1))) unsigned int gu32_t;
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 #define PICP_MAX_PBLK 256   // max blocks per problem in this mode (sweep registers)
 #define PICP_PBLOCK 512     // the partition's unit: npt items per lane of a 512-thread block
-// -DPICP_PWIDE=1 (A/B): npt 8 (4096 items per block, C3) as 1024 threads x 4 items, four waves
-// per SIMD instead of two within 128 VGPRs.  Alone, that linearize is 11 % faster than 512 x 8
-// (tools/ubench/lin_ubench.hip at 97 VGPRs); inside this kernel, squeezed to 128 VGPRs next to the
-// hand-off code, the leader's linearize + publish took 3.9 instead of 3.5 us and C3 did not move
-// (139-141k it/s both; profiles/r03/pwide/).
-#ifndef PICP_PWIDE
-#define PICP_PWIDE 0
-#endif
-// Followers' pose wait: two polls in flight this many s_sleep units (64 clocks) apart (0: one)
-#ifndef PICP_POSE_STAGGER
+// (npt 8 as 1024 threads x 4 items did not move C3: DESIGN.md Appendix A, "1024 x 4".)
+// Followers' pose wait: two polls in flight this many s_sleep units (64 clocks) apart
 #define PICP_POSE_STAGGER 8
-#endif
-// The solvers' sweep with two passes in flight, PICP_SWEEP_STAGGER x 64 clocks apart (0: one
-// pass at a time).  Each pass loads every pending granule pair (the others point past the buffer's
+// The solvers' sweep with two passes in flight, PICP_SWEEP_STAGGER x 64 clocks apart.
+// Each pass loads every pending granule pair (the others point past the buffer's
 // range: no memory access, a zero), so both passes' loads are unconditional and the waits count
 // exactly one pass.  C3 150.5k -> 156.5k it/s (8 x 64 clocks; 16: 155k); with one item per lane
 // (C2) -2 %, so it starts at PICP_SWEEP_MIN_NPT items (profiles/r05/sweep_stagger/).
-#ifndef PICP_SWEEP_STAGGER
 #define PICP_SWEEP_STAGGER 8
-#endif
-#ifndef PICP_SWEEP_MIN_NPT  // the staggered sweep from this many items per lane on
-#define PICP_SWEEP_MIN_NPT 2
-#endif
-#ifndef PICP_POSE_NPOLL  // polls in flight in the followers' pose wait (2 or 3), when staggered
-#define PICP_POSE_NPOLL 2
-#endif
+#define PICP_SWEEP_MIN_NPT 2  // the staggered sweep from this many items per lane on
 #define PICP_POSE_GRAN 16   // pose granules per set: R(9) t(3) done(1) solver XCC id(1) pad(2)
-// Solver blocks per problem (-DPICP_PSOLVERS=1 for A/B: one leader, every follower polling its
-// agent-scope pose).  Blocks kb and kb + 8j share an XCD under round-robin placement, so solver
+// Solver blocks per problem.  Blocks kb and kb + 8j share an XCD under round-robin placement, so solver
 // kb & 7 publishes where its followers' polls are L2 hits instead of fabric round trips: an
 // agent-scope (sc1) store drops its line from the writer's L2 (MI355X_MICROARCH.md), a
 // workgroup-scope (sc0) store keeps it there.  Placement is not guaranteed, so the solver also
 // publishes agent-scope and carries its XCC id; a follower on another XCD polls that copy.
-#ifndef PICP_PSOLVERS
 #define PICP_PSOLVERS 8
-#endif
 // each solver owns two pose sets (its L2 copy and its agent-scope copy) of the problem's region
 static_assert(2 * PICP_PSOLVERS <= PICP_POSE_SETS, "PICP_PSOLVERS needs 2 pose sets each (picp_internal.h)");
 // (A timeout in one solver ends its followers' waits; the other solvers then wait out their own
@@ -106,15 +87,7 @@ __device__ __forceinline__ unsigned long long granule(unsigned epoch, float v) {
   return ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v);
 }
 
-// hand-off polls run back to back: an s_sleep 1 (64 clocks) between polls measured C2 214-223k
-// vs 222-225k it/s without it, bimodal vs steady (C3 unchanged; profiles/r02/e3/ab_spin.log).
-// -DPICP_POLL_SLEEP restores the pause for A/B runs.
-#ifdef PICP_POLL_SLEEP
-#define PICP_POLL_PAUSE() __builtin_amdgcn_s_sleep(1)
-#else
-#define PICP_POLL_PAUSE() ((void)0)
-#endif
-
+// (hand-off polls run back to back: a pause between them lost, DESIGN.md Appendix A "poll sleep")
 __device__ __forceinline__ bool timed_out(unsigned long long deadline) {
   return __builtin_amdgcn_s_memrealtime() > deadline;
 }
@@ -125,7 +98,13 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     const float* __restrict__ U, const float* __restrict__ V, const PicpArgs A,
     const PicpState* __restrict__ st_in, PicpState* __restrict__ st_out,
     unsigned long long* gpart, unsigned long long* gpose, unsigned int* err, unsigned int* tagbase,
-    unsigned long long* arrive, unsigned long long timeout_ticks) {
+    unsigned long long* unused_slot, unsigned long long timeout_ticks) {
+  // unused_slot (always null): the kernel-argument slot of the deleted arrival counter.  Dropping
+  // it moves timeout_ticks' kernarg offset and with it the NPT = 8 schedule (about 380 of 4,400
+  // instructions reordered, same registers); the C2/C3 A/B of that build had one C3 median 0.06 %
+  // under the parent's band (profiles/r07/prune/ab.log), so the slot stays and the code is the
+  // measured one.
+  (void)unused_slot;
   __shared__ double s_red[PICP_NPART][BS / 64];  // term-major: one row per combining lane
   __shared__ float s_tot[PICP_NPART];
   __shared__ float s_wave[BS / 64][PICP_NPART];
@@ -160,15 +139,8 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   // and no memset node has to clear the granules before each launch.
   gu32_t* tbase_p = ((gu32_t*)tagbase) + p;
   const unsigned tbase = __hip_atomic_load(tbase_p, RLX_AGENT);
-#ifdef PICP_ARRIVAL
-  // A/B: a per-problem count of block publishes, on a line of its own.  It
-  // tracks tbase * nblk across launches (both zeroed together by the host), so round e is complete
-  // at (tbase + e) * nblk.  The solvers wait on it before the sweep -- a hint only: the sweep
-  // still checks every granule's tag, so a late or reordered count costs time, never a result.
-  gu64_t* arrive_p = ((gu64_t*)arrive) + (size_t)p * 16;
-#else
-  (void)arrive;
-#endif
+  // (A per-problem arrival counter the solvers waited on before the sweep halved C2 and C3:
+  // DESIGN.md Appendix A, "arrival counter".)
 
   // this block's slice, loaded once into registers (coalesced: item = tid + k*BLOCK)
   float xs[NPT], ys[NPT], zs[NPT], us[NPT], vs[NPT];
@@ -214,7 +186,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   const bool keep = A.keep_outliers != 0;
 
   float chi_prev = FLT_MAX;  // the leader's loop state besides the pose (exec/icp_test.cpp:89)
-  unsigned long long pose_sink = 0, pa = 0, pb = 0, pc = 0;  // the follower's pose polls (PICP_POSE_STAGGER)
+  unsigned long long pose_sink = 0, pa = 0, pb = 0;  // the follower's pose polls
   for (unsigned epoch = 1; !s_done; ++epoch) {
     // every wait of this round is bounded from the round's start (a whole solve may take far
     // longer than timeout_ticks at large max_rounds; one round never does)
@@ -266,20 +238,10 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
 #pragma unroll
       for (int w = 1; w < BS / 64; ++w) sum += s_wave[w][tid];
       __hip_atomic_store(my_part0 + (epoch & 1) * part_stride + tid, granule(tbase + epoch, sum), RLX_AGENT);
-#ifdef PICP_ARRIVAL
-      if (tid == 0) __hip_atomic_fetch_add(arrive_p, 1ull, RLX_AGENT);  // after wave 0's granule stores
-#endif
     }
     PSTAMP(1);
 
     if (solver) {
-#ifdef PICP_ARRIVAL
-      {
-        const unsigned long long target = (unsigned long long)(tbase + epoch) * (unsigned)nblk;
-        while (__hip_atomic_load(arrive_p, RLX_AGENT) < target && !timed_out(deadline)) {
-        }
-      }
-#endif
       // ---- 2. sweep the problem's partials: 16-B sc1 loads of granule pairs (2c, 2c+1) of
       //         blocks g + NG*i (c = tid&15, g = tid>>4); each 8-B half carries its own tag ----
       const int c = tid & 15, g = tid >> 4;
@@ -357,7 +319,6 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
             s_tmo = 1;
             break;
           }
-          PICP_POLL_PAUSE();
         }
       }
       double acc0 = 0.0, acc1 = 0.0;
@@ -412,7 +373,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           // the wave finishes the round (every lane the same values, loop state in registers)
           RoundOut o;
           PSTAMP(4);
-          finish_round_pose<PICP_FINISH_WAVE>(A, s_tot, (int)epoch, pr, pt, chi_prev, o);
+          finish_round_pose(A, s_tot, (int)epoch, pr, pt, chi_prev, o);
           PSTAMP(5);
           if (s_tmo) o.done = 1;  // a sweep timed out
           // ---- publish the new pose (and the done flag): lane l < 16 owns word l ----
@@ -425,8 +386,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           w = (lane == 13) ? __uint_as_float(my_xcc) : w;
           if (lane < PICP_POSE_GRAN) {
             const unsigned long long gw = granule(tbase + epoch, w);
-            if (PICP_PSOLVERS > 1)
-              __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
           }
           if (lane == 0) {
@@ -450,7 +410,6 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       // ---- 3. wait for the leader's pose of this round (one wave, 16 lanes) ----
       if (wave == 0) {
         unsigned long long gp = 0;
-#if PICP_POSE_STAGGER > 0
         // Two polls in flight, PICP_POSE_STAGGER x 64 clocks apart: each poll is re-issued as soon
         // as it has been checked, so the pair keeps its offset and the pose is seen within about
         // half a round trip of landing instead of a whole one (two polls issued together, checked
@@ -460,68 +419,36 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
         // nothing waits on it.
         const int gl = lane < PICP_POSE_GRAN ? lane : PICP_POSE_GRAN - 1;
         // sc1 loads either way: past the L1, served by the L2 (the L2 copy's line stays there)
-        const gu64_t* src = (PICP_PSOLVERS > 1 && s_l2) ? pose_l2 : pose_gl;
+        const gu64_t* src = s_l2 ? pose_l2 : pose_gl;
         auto poll = [&]() -> unsigned long long { return __hip_atomic_load(src + gl, RLX_AGENT); };
         auto good = [&](unsigned long long v) { return __all((unsigned)(v >> 32) == tbase + epoch); };
-        pose_sink ^= pa ^ pb ^ pc;  // last round's polls: long complete
+        pose_sink ^= pa ^ pb;  // last round's polls: long complete
         bool tmo = false;
         pa = poll();
         __builtin_amdgcn_s_sleep(PICP_POSE_STAGGER);
-        if constexpr (PICP_POSE_NPOLL >= 3) {
+        for (;;) {
           pb = poll();
-          __builtin_amdgcn_s_sleep(PICP_POSE_STAGGER);
-          for (;;) {
-            pc = poll();
-            if (good(pa)) { gp = pa; break; }
-            pa = poll();
-            if (good(pb)) { gp = pb; break; }
-            pb = poll();
-            if (good(pc)) { gp = pc; break; }
-            if (timed_out(deadline)) { tmo = true; break; }
-          }
-        } else {
-          for (;;) {
-            pb = poll();
-            if (good(pa)) { gp = pa; break; }
-            pa = poll();
-            if (good(pb)) { gp = pb; break; }
-            if (timed_out(deadline)) { tmo = true; break; }
-          }
+          if (good(pa)) { gp = pa; break; }
+          pa = poll();
+          if (good(pb)) { gp = pb; break; }
+          if (timed_out(deadline)) { tmo = true; break; }
         }
         if (tmo) {
           if (lane == 0) __hip_atomic_store(errw, 2u, RLX_AGENT);
           gp = lane == 12 ? 1u : 0u;  // force done
           if (lane < 12) gp = __float_as_uint(s_pose[lane]);
         }
-#else
-        const gu64_t* src = (PICP_PSOLVERS > 1 && s_l2) ? pose_l2 : pose_gl;
-        for (;;) {
-          bool ok = true;
-          if (lane < PICP_POSE_GRAN) {
-            gp = __hip_atomic_load(src + lane, RLX_AGENT);
-            ok = (unsigned)(gp >> 32) == tbase + epoch;
-          }
-          if (__all(ok)) break;
-          if (timed_out(deadline)) {
-            if (lane == 0) __hip_atomic_store(errw, 2u, RLX_AGENT);
-            gp = lane == 12 ? 1u : 0u;  // force done
-            if (lane < 12) gp = __float_as_uint(s_pose[lane]);
-            break;
-          }
-          PICP_POLL_PAUSE();
-        }
-#endif
         if (lane < 12) s_pose[lane] = __uint_as_float((unsigned)gp);
         if (lane == 12) s_done = (int)(unsigned)gp;
         // the solver's XCC id: from the next round on, poll the L2 copy when it is this XCD's
-        if (PICP_PSOLVERS > 1 && lane == 13) s_l2 = ((unsigned)gp == my_xcc) ? 1 : 0;
+        if (lane == 13) s_l2 = ((unsigned)gp == my_xcc) ? 1 : 0;
       }
       __syncthreads();
       PSTAMP(2);
     }
   }
   // an opaque never-true test keeps the follower's last in-flight poll alive to here
-  if (timeout_ticks == ~0ull && (pose_sink ^ pa ^ pb ^ pc) == 1ull) s_pose[0] = 0.0f;
+  if (timeout_ticks == ~0ull && (pose_sink ^ pa ^ pb) == 1ull) s_pose[0] = 0.0f;
 }
 
 #ifdef PICP_STAMPS
@@ -545,20 +472,12 @@ extern "C" hipError_t picp_debug_sweepstamps(unsigned long long* out, size_t n_w
 // ------------------------------- host launch wrapper -------------------------------
 extern "C" int picp_persistent_block(void) { return PICP_PBLOCK; }
 
-// npt (items per lane of a 512-thread block) -> the kernel's items per lane and block size
-template <int N>
-struct PShape {
-  static constexpr int npt = (PICP_PWIDE && N == 8) ? 4 : N;
-  static constexpr int bs = (PICP_PWIDE && N == 8) ? 1024 : PICP_PBLOCK;
-};
-
 template <int N>
 static const void* persistent_kernel_n(int var) {
-  constexpr int T = PShape<N>::npt, B = PShape<N>::bs;
   switch (var) {
-    case PICP_V_PINHOLE: return (const void*)picp_persistent_kernel<T, PICP_V_PINHOLE, B>;
-    case PICP_V_PINHOLE_KEEP: return (const void*)picp_persistent_kernel<T, PICP_V_PINHOLE_KEEP, B>;
-    default: return (const void*)picp_persistent_kernel<T, PICP_V_GENERAL, B>;
+    case PICP_V_PINHOLE: return (const void*)picp_persistent_kernel<N, PICP_V_PINHOLE, PICP_PBLOCK>;
+    case PICP_V_PINHOLE_KEEP: return (const void*)picp_persistent_kernel<N, PICP_V_PINHOLE_KEEP, PICP_PBLOCK>;
+    default: return (const void*)picp_persistent_kernel<N, PICP_V_GENERAL, PICP_PBLOCK>;
   }
 }
 
@@ -578,8 +497,7 @@ extern "C" hipError_t picp_persistent_occupancy(int npt, const float K[9], int* 
       default: return hipErrorInvalidValue;
     }
     int occ = 0;
-    const hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, npt == 8 ? PShape<8>::bs : PICP_PBLOCK, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, PICP_PBLOCK, 0);
     if (e != hipSuccess) return e;
     best = (best < 0 || occ < best) ? occ : best;
   }
@@ -593,13 +511,13 @@ extern "C" hipError_t picp_launch_persistent(hipStream_t stream, int grid, int n
                                              const PicpState* st_in, PicpState* st_out,
                                              unsigned long long* gpart, unsigned long long* gpose,
                                              unsigned int* err, unsigned int* tagbase,
-                                             unsigned long long* arrive, unsigned long long timeout_ticks) {
+                                             unsigned long long timeout_ticks) {
   if (grid <= 0 || !args || !args->uniform || args->nblk_u > PICP_MAX_PBLK) return hipErrorInvalidValue;
   const int var = picp_variant(args->K, args->keep_outliers);
-#define PICP_LAUNCH_PV(N, PV)                                                                      \
-  hipLaunchKernelGGL((picp_persistent_kernel<PShape<N>::npt, PV, PShape<N>::bs>), dim3(grid),      \
-                     dim3(PShape<N>::bs), 0, stream, X, Y, Z, U, V, *args, st_in, st_out, gpart, gpose, \
-                     err, tagbase, arrive, timeout_ticks)
+#define PICP_LAUNCH_PV(N, PV)                                                                       \
+  hipLaunchKernelGGL((picp_persistent_kernel<N, PV, PICP_PBLOCK>), dim3(grid), dim3(PICP_PBLOCK), 0, \
+                     stream, X, Y, Z, U, V, *args, st_in, st_out, gpart, gpose, err, tagbase,         \
+                     (unsigned long long*)nullptr, timeout_ticks)
 #define PICP_LAUNCH_P(N)                                                            \
   if (var == PICP_V_PINHOLE) PICP_LAUNCH_PV(N, PICP_V_PINHOLE);                     \
   else if (var == PICP_V_PINHOLE_KEEP) PICP_LAUNCH_PV(N, PICP_V_PINHOLE_KEEP);      \

@@ -37,9 +37,7 @@ using namespace picp;
 // The append kernel triangulates with every lane of its block (FP64 Jacobi per new point): a
 // wider block puts four waves on each SIMD instead of one, so the FP64 chains of different
 // points overlap.  Its compaction covers 4096 / VOA_BLOCK chunks of VOA_BLOCK (4096 observations).
-#ifndef VOA_BLOCK
 #define VOA_BLOCK 512  // 2 waves per SIMD (152 VGPRs); 1024 spills (profiles/r01/vo_append_ab.log)
-#endif
 
 __global__ __launch_bounds__(VO_BLOCK) void vo_gather_kernel(const VoArgs a, int t) {
   const int s = a.seg0 + (int)blockIdx.x;
@@ -136,14 +134,4 @@ extern "C" hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a,
   if (!a || a->n_seg <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(vo_append_kernel, dim3(a->n_seg), dim3(VOA_BLOCK), 0, stream, *a, t);
   return hipGetLastError();
-}
-
-// 1 when this library's device code was built with packed FP32 (make PK=1, A/B builds only): the
-// VO runtime then defaults to the serial schedule
-extern "C" int picp_build_packed_fp32(void) {
-#ifdef PICP_ALLOW_PK
-  return 1;
-#else
-  return 0;
-#endif
 }

@@ -31,7 +31,6 @@ extern "C" hipError_t picp_launch_block(hipStream_t stream, int n_problems, int 
                                         unsigned int* tagbase, unsigned long long timeout_ticks);
 extern "C" hipError_t picp_launch_vo_gather(hipStream_t stream, const VoArgs* a, int t);
 extern "C" int picp_vo_block_fusable(int npt, int64_t max_obs);
-extern "C" int picp_build_packed_fp32(void);
 extern "C" hipError_t picp_launch_vo_block(hipStream_t stream, const VoArgs* a, int t, int npt,
                                            const PicpArgs* args, int64_t max_obs);
 extern "C" hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a, int t);
@@ -130,7 +129,6 @@ struct picp_vo {
   std::vector<char> split_c;          // [chains]
   std::vector<float4*> part_e;        // [chains][2]: early ranges + the late slot, by step parity
   std::vector<int64_t> cap_e;         // [chains]
-  std::vector<int> ks_e;              // [chains]: the early part's range split (PICP_VO_EKS forces)
   std::vector<hipStream_t> estream;   // [chains]
   std::vector<hipEvent_t> ev_app;     // [chains]: the chain's latest merged match
   std::vector<hipEvent_t> ev_early;   // [chains][2]: the early part of step t done (by parity)
@@ -253,14 +251,6 @@ extern "C" int picp_vo_create(picp_vo_t** out, int device, int rows, int cols, c
     h->graph_env = true;
   }
   if (const char* e = getenv("PICP_VO_MATCH_FULL")) h->accept_only = atoi(e) != 0 ? 0 : 1;
-  // A/B libraries built with packed FP32 (make PK=1): their concurrent schedules are not
-  // bit-stable, so such a build defaults to the serial order and says so
-  if (picp_build_packed_fp32()) {
-    h->overlap = false;
-    h->chains = 1;
-    fprintf(stderr, "picp_vo_create: this library was built with packed FP32 (make PK=1, an A/B build): the "
-                    "VO schedule defaults to the serial order; concurrent schedules are not bit-stable with it\n");
-  }
   if (const char* e = getenv("PICP_VO_OVERLAP")) h->overlap = atoi(e) != 0;
   // at most two groups: three and four measured slower at the default shape (C5 592k / 404k vs
   // 597-600k frames/s with two, round 2), and so did four and eight at the
@@ -314,23 +304,8 @@ extern "C" int picp_vo_create(picp_vo_t** out, int device, int rows, int cols, c
       h->estream.assign((size_t)h->chains, nullptr);
       h->ev_app.assign((size_t)h->chains, nullptr);
       h->ev_early.assign((size_t)2 * h->chains, nullptr);
-      // A/B (PICP_VO_ECU_SKIP=k): the early parts on CU-masked queues leaving every k-th CU to
-      // the step chains (a CU-masked stream has the default priority)
-      const char* cm = getenv("PICP_VO_ECU_SKIP");
-      std::vector<uint32_t> mask;
-      if (cm && atoi(cm) >= 2) {
-        int ncu = 0;
-        HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        const int k = atoi(cm);
-        mask.assign((size_t)(ncu + 31) / 32, 0u);
-        for (int i = 0; i < ncu; ++i)
-          if (i % k != k - 1) mask[(size_t)i / 32] |= 1u << (i % 32);
-      }
       for (int c = 0; c < h->chains; ++c) {
-        if (!mask.empty())
-          HIP_TRY(hipExtStreamCreateWithCUMask(&h->estream[c], (uint32_t)mask.size(), mask.data()));
-        else
-          HIP_TRY(hipStreamCreateWithPriority(&h->estream[c], hipStreamNonBlocking, lo));
+        HIP_TRY(hipStreamCreateWithPriority(&h->estream[c], hipStreamNonBlocking, lo));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_app[c], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_early[2 * c], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_early[2 * c + 1], hipEventDisableTiming));
@@ -497,16 +472,11 @@ extern "C" int picp_vo_set_segments(picp_vo_t* h, int n_seg, const int64_t* firs
   // slot for the late part (2 buffers: step t's merge and step t+2's early part overlap)
   std::vector<char> split_c((size_t)chains_eff, 0);
   std::vector<int64_t> cap_e((size_t)chains_eff, 0);
-  std::vector<int> ks_e((size_t)chains_eff, 1);
-  const char* eks = getenv("PICP_VO_EKS");
   std::vector<Part> p_parte;
   for (int c = 0; c < chains_eff; ++c) {
     const int nsc = (int)((int64_t)n_seg * (c + 1) / chains_eff - (int64_t)n_seg * c / chains_eff);
     split_c[c] = !h->estream.empty() && (h->split_env == 1 || (h->split_env < 0 && ks_w[c] > 1));
-    ks_e[c] = (eks && atoi(eks) > 0) ? std::max(picp_match_ksplit_forced(nsc, h->max_obs, max_map, ks_form,
-                                                                         atoi(eks)), 1)
-                                     : ks_w[c];
-    if (split_c[c]) cap_e[c] = (int64_t)(ks_e[c] + 1) * nsc * std::max<int64_t>(h->max_obs, 1);
+    if (split_c[c]) cap_e[c] = (int64_t)(ks_w[c] + 1) * nsc * std::max<int64_t>(h->max_obs, 1);
     p_parte.push_back(part((size_t)2 * cap_e[c] * sizeof(float4)));
   }
   // the frame->next launches, as vo_frame_match issues them: the whole table up front (overlap off)
@@ -547,7 +517,6 @@ extern "C" int picp_vo_set_segments(picp_vo_t* h, int n_seg, const int64_t* firs
     if (p_partw[c].bytes) h->part_w[c] = (float4*)(m + p_partw[c].off);
   h->split_c = split_c;
   h->cap_e = cap_e;
-  h->ks_e = ks_e;
   h->part_e.assign((size_t)2 * chains_eff, nullptr);
   for (int c = 0; c < chains_eff; ++c)
     if (split_c[c]) {
@@ -736,7 +705,7 @@ static hipError_t vo_enqueue(picp_vo* h) {
     if (!(skip & 8))
       r = picp_launch_match_mfma_parts(es, V.n_seg, h->max_obs, h->desc_d, V.map_desc, h->obs_h, h->obs_n1,
                                        V.map_h, V.map_n1, V.map_n2, V.eprobs + (size_t)p * h->n_seg + V.seg0,
-                                       h->dim, VO_MATCH_DIST, VO_MATCH_RATIO, h->accept_only, h->ks_e[c], 0,
+                                       h->dim, VO_MATCH_DIST, VO_MATCH_RATIO, h->accept_only, h->ks_w[c], 0,
                                        h->part_e[2 * c + p], h->cap_e[c]);
     if (r == hipSuccess) r = hipEventRecord(h->ev_early[2 * c + p], es);
     return r;
@@ -789,11 +758,11 @@ static hipError_t vo_enqueue(picp_vo* h) {
         if (e == hipSuccess && !(skip & 8))
           e = picp_launch_match_mfma_parts(st, V.n_seg, h->max_obs, h->desc_d, V.map_desc, h->obs_h, h->obs_n1,
                                            V.map_h, V.map_n1, V.map_n2, V.lprobs + s0, h->dim, VO_MATCH_DIST,
-                                           VO_MATCH_RATIO, h->accept_only, 1, h->ks_e[c], h->part_e[2 * c + p],
+                                           VO_MATCH_RATIO, h->accept_only, 1, h->ks_w[c], h->part_e[2 * c + p],
                                            h->cap_e[c]);
         if (e == hipSuccess && !(skip & 8))
-          e = picp_launch_match_merge(st, V.eprobs + (size_t)p * h->n_seg + s0, V.n_seg, h->max_obs, h->ks_e[c],
-                                      h->ks_e[c], h->part_e[2 * c + p], h->cap_e[c], VO_MATCH_DIST, VO_MATCH_RATIO,
+          e = picp_launch_match_merge(st, V.eprobs + (size_t)p * h->n_seg + s0, V.n_seg, h->max_obs, h->ks_w[c],
+                                      h->ks_w[c], h->part_e[2 * c + p], h->cap_e[c], VO_MATCH_DIST, VO_MATCH_RATIO,
                                       h->wm_bi, h->wm_bd, h->wm_sd, h->wm_acc);
       } else if (e == hipSuccess && !(skip & 8)) {
         e = world_match(st, V, h->wprobs_d, c);
