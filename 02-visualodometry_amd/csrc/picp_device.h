@@ -326,6 +326,44 @@ __device__ __forceinline__ void accumulate_pinhole(const Pose& T, const Cam& C, 
   }
 }
 
+// The state of one correspondence at a pose (include/picp_c.h PICP_CORR_*: 0 skipped, 1 inlier,
+// 2 outlier) with its chi2 and projection (-1 where skipped): the projection, bounds test, error
+// and chi2 of accumulate_one (general K) or accumulate_pinhole (pinhole K: the zero terms of K
+// dropped, ph2 == pc2) restated with contraction off, in their operation order and with the
+// IEEE division, so all three are bit-identical to the oracle's or_error_and_jacobian /
+// or_project_point at the same pose -- and so to what the solve kernels decide.  The accumulate
+// functions are deliberately not rewritten on top of this one: their code stays as measured.
+__device__ __forceinline__ int classify_item(const Pose& T, const Cam& C, float thr, bool pinhole,
+                                             float x, float y, float z, float u, float v,
+                                             float* chi_out, float* iu, float* iv) {
+#pragma clang fp contract(off)
+  const float pc0 = ((T.r00 * x + T.r01 * y) + T.r02 * z) + T.t0;  // src/camera.h:26
+  const float pc1 = ((T.r10 * x + T.r11 * y) + T.r12 * z) + T.t1;
+  const float pc2 = ((T.r20 * x + T.r21 * y) + T.r22 * z) + T.t2;
+  float ph0, ph1, ph2;
+  if (pinhole) {  // uniform
+    ph0 = C.k00 * pc0 + C.k02 * pc2;  // src/camera.h:29 without the zero terms
+    ph1 = C.k11 * pc1 + C.k12 * pc2;
+    ph2 = pc2;
+  } else {
+    ph0 = (C.k00 * pc0 + C.k01 * pc1) + C.k02 * pc2;
+    ph1 = (C.k10 * pc0 + C.k11 * pc1) + C.k12 * pc2;
+    ph2 = (C.k20 * pc0 + C.k21 * pc1) + C.k22 * pc2;
+  }
+  const float iz = 1.0f / ph2;  // src/camera.h:30, correctly rounded
+  const float ix = ph0 * iz;
+  const float iy = ph1 * iz;
+  // src/camera.h:27-28 (z <= 0 rejects; NaN passes as in the reference) and :31-34
+  const bool valid = !(pc2 <= 0.0f) & !((ix < 0.0f) | (ix > C.maxx) | (iy < 0.0f) | (iy > C.maxy));
+  const float e0 = ix - u;  // src/picp_solver.cpp:34
+  const float e1 = iy - v;
+  const float chi = e0 * e0 + e1 * e1;  // src/picp_solver.cpp:74
+  *chi_out = valid ? chi : -1.0f;
+  *iu = valid ? ix : -1.0f;
+  *iv = valid ? iy : -1.0f;
+  return valid ? ((chi > thr) ? 2 : 1) : 0;  // src/picp_solver.cpp:77, strict gate
+}
+
 // The general-K per-item math of accumulate_one up to the weighted Jacobian (for the packed
 // pair accumulation): outputs are zeroed for an unused item, w is its kernel weight.
 struct Item {

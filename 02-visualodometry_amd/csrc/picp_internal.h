@@ -68,6 +68,14 @@ struct PicpState {
   int32_t pad[11];
 };
 
+// classify pass (picp_classify.hip): camera, gate and per-item path, by value
+struct ClsArgs {
+  float K[9];          // camera matrix, column-major
+  float maxx, maxy;    // cols-1, rows-1
+  float threshold;     // chi2 gate
+  int32_t pinhole;     // 1: the pinhole-K operation order (accumulate_pinhole), 0: general K
+};
+
 static_assert(sizeof(PicpState) == 128, "PicpState must be 128 B");
 static_assert(sizeof(PicpProblem) % 8 == 0, "PicpProblem alignment");
 

@@ -34,6 +34,8 @@ extern "C" int picp_vo_block_fusable(int npt, int64_t max_obs);
 extern "C" hipError_t picp_launch_vo_block(hipStream_t stream, const VoArgs* a, int t, int npt,
                                            const PicpArgs* args, int64_t max_obs);
 extern "C" hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a, int t);
+extern "C" hipError_t picp_launch_vo_track(hipStream_t stream, const VoArgs* a, int t, const ClsArgs* c,
+                                           int* n_matched, int* n_inlier);
 
 static_assert(sizeof(picp_vo_step) == sizeof(VoStep), "picp_vo_step must mirror VoStep");
 
@@ -140,6 +142,12 @@ struct picp_vo {
   // (the append fused after the rounds and a world match split into an early and a late part were
   // built in round 4, bit-identical, and measured slower: DESIGN.md §4.14, commit 1ffa87f)
   int fuse = 1;  // PICP_VO_FUSE: 0 separate gather, 1 gather in the PICP kernel
+  // per-map-point track counters (picp_vo_set_track_stats; off by default): n_matched |
+  // n_inlier, track_slots int32 each, zeroed at the start of every run and filled by one
+  // vo_track_kernel launch per chain step between the PICP launch and the append
+  bool track = false;
+  int32_t* track_d = nullptr;
+  int64_t track_slots = 0;
   bool guard = false;
   std::vector<VoGuarded> guards;
 #ifdef PICP_VO_DIAG
@@ -191,7 +199,7 @@ extern "C" int picp_vo_destroy(picp_vo_t* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   vo_free_segments(h);
   void* bufs[] = {h->frame_off_d, h->uv_d, h->desc_d, h->pm_bi, h->pm_acc, h->wm_bi, h->wm_acc,
-                  h->pm_bd, h->pm_sd, h->wm_bd, h->wm_sd, h->obs_h, h->obs_n1, h->obs_n2};
+                  h->pm_bd, h->pm_sd, h->wm_bd, h->wm_sd, h->obs_h, h->obs_n1, h->obs_n2, h->track_d};
   for (void* p : bufs)
     if (p) vo_dfree(h, p);
   if (h->ev0) hipEventDestroy(h->ev0);
@@ -345,6 +353,19 @@ extern "C" int picp_vo_create(picp_vo_t** out, int device, int rows, int cols, c
 }
 
 static int64_t frame_n(const picp_vo* h, int64_t f) { return h->frame_off[f + 1] - h->frame_off[f]; }
+
+// the track counters for the current segments' map (tracking on, segments set)
+static int vo_track_alloc(picp_vo* h) {
+  if (!h->track || h->n_seg <= 0 || h->track_slots >= h->map_slots) return PICP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->track_d) vo_dfree(h, h->track_d);
+  h->track_d = nullptr;
+  h->track_slots = 0;
+  HIP_TRY(vo_malloc(h, (void**)&h->track_d, 2 * (size_t)h->map_slots * sizeof(int32_t), "track"));
+  HIP_TRY(hipMemset(h->track_d, 0, 2 * (size_t)h->map_slots * sizeof(int32_t)));
+  h->track_slots = h->map_slots;
+  return PICP_OK;
+}
 
 extern "C" int picp_vo_set_segments(picp_vo_t* h, int n_seg, const int64_t* first,
                                     const int32_t* steps, const float* boot_poses,
@@ -601,7 +622,7 @@ extern "C" int picp_vo_set_segments(picp_vo_t* h, int n_seg, const int64_t* firs
   V.map_n2 = (float*)(m + p_mn2.off);
   h->wprobs_d = V.wprobs;
   h->pprobs_d = (MatchProblem*)(m + p_pprobs.off);
-  return PICP_OK;
+  return vo_track_alloc(h);
 }
 
 // frame->next match problems [p0, p1) on stream st, in launches of at most VO_MAX_GRID_Y problems
@@ -685,6 +706,18 @@ static hipError_t vo_enqueue(picp_vo* h) {
 #endif
   const size_t nck = h->chunk_off.size() - 1;
   const bool ov = h->overlap && nck > 1;
+  // track counters: zeroed before anything of the run (the chains' streams fork from this one)
+  const bool track = h->track && h->track_d && h->track_slots >= h->map_slots;
+  ClsArgs targs;
+  memset(&targs, 0, sizeof(targs));
+  memcpy(targs.K, h->K, sizeof(targs.K));
+  targs.maxx = h->pargs.maxx;
+  targs.maxy = h->pargs.maxy;
+  targs.threshold = h->pargs.threshold;
+  if (track) {
+    hipError_t ez = hipMemsetAsync(h->track_d, 0, 2 * (size_t)h->track_slots * sizeof(int32_t), h->stream);
+    if (ez != hipSuccess) return ez;
+  }
   hipError_t e = vo_frame_match(h, h->stream, 0, ov ? h->chunk_off[1] : h->chunk_off[nck]);
   if (e == hipSuccess && ov) {
     e = hipEventRecord(h->ev_fork, h->stream);
@@ -788,6 +821,9 @@ static hipError_t vo_enqueue(picp_vo* h) {
 #ifdef PICP_VO_DIAG
       if (e == hipSuccess) e = vo_snap(h, st, t, s0, s1);
 #endif
+      // wm_* and st_out are both this step's here (the append below writes the next step's)
+      if (e == hipSuccess && track)
+        e = picp_launch_vo_track(st, &V, t, &targs, h->track_d, h->track_d + h->track_slots);
       if (e == hipSuccess && ov && t >= 1) e = hipStreamWaitEvent(st, h->ev_chunk[t], 0);
       if (e == hipSuccess && !(skip & 2)) e = picp_launch_vo_append(st, &V, t);
     }
@@ -882,6 +918,40 @@ extern "C" int picp_vo_get_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, f
   if (desc && k)
     HIP_TRY(hipMemcpy(desc, h->vargs.map_desc + off * h->dim, (size_t)k * h->dim * sizeof(float),
                       hipMemcpyDeviceToHost));
+  return PICP_OK;
+}
+
+extern "C" int picp_vo_set_track_stats(picp_vo_t* h, int enable) {
+  CHECK_ARG(h, "picp_vo_set_track_stats: null handle");
+  const bool on = enable != 0;
+  if (on == h->track) return PICP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->track = on;
+  // the captured sequence has (or lacks) the track launches: capture again at the next run
+  if (h->exec) hipGraphExecDestroy(h->exec);
+  if (h->graph) hipGraphDestroy(h->graph);
+  h->exec = nullptr;
+  h->graph = nullptr;
+  return vo_track_alloc(h);
+}
+
+extern "C" int picp_vo_get_map_stats(picp_vo_t* h, int seg, int64_t cap, int32_t* n_matched, int32_t* n_inlier,
+                                     int64_t* n) {
+  CHECK_ARG(h && n && h->n_seg > 0 && seg >= 0 && seg < h->n_seg, "picp_vo_get_map_stats: bad argument");
+  if (!h->track || !h->track_d)
+    return picp_set_err(PICP_ERR_STATE, "picp_vo_get_map_stats: tracking is off (picp_vo_set_track_stats)");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  int64_t mn = 0;
+  HIP_TRY(hipMemcpy(&mn, h->vargs.map_n + seg, sizeof(int64_t), hipMemcpyDeviceToHost));
+  *n = mn;
+  const int64_t k = std::min(mn, std::max<int64_t>(cap, 0));
+  const int64_t off = h->segs[seg].map_off;
+  if (n_matched && k)
+    HIP_TRY(hipMemcpy(n_matched, h->track_d + off, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (n_inlier && k)
+    HIP_TRY(hipMemcpy(n_inlier, h->track_d + h->track_slots + off, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost));
   return PICP_OK;
 }
 

@@ -47,7 +47,11 @@ EXPORTED = [
     "picp_vo_info", "picp_selftest_rcp", "picp_essential_params_default", "picp_essential_batch",
     "picp_shard_range", "picp_shard_pad", "picp_shard_unpack", "picp_comm_unique_id", "picp_comm_create", "picp_comm_destroy", "picp_comm_info",
     "picp_comm_allreduce_max", "picp_comm_barrier", "picp_batch_allgather", "picp_batch_allgather_host",
+    "picp_classify", "picp_batch_classify", "picp_batch_classify_time",
+    "picp_vo_set_track_stats", "picp_vo_get_map_stats",
 ]
+# state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
+CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
 COMM_ID_BYTES = 128
 
 
@@ -165,6 +169,14 @@ def lib():
         "picp_comm_barrier": ([vp], i),
         "picp_batch_allgather": ([vp, vp, i64, fp, sp], i),
         "picp_batch_allgather_host": ([vp, i, i, EXCHANGE_FN, vp, i64, fp, sp], i),
+        "picp_classify": ([vp, f, ctypes.POINTER(ctypes.c_uint8), fp, fp, ctypes.POINTER(ctypes.c_int32),
+                           ctypes.POINTER(i64)], i),
+        "picp_batch_classify": ([vp, f, fp, ctypes.POINTER(ctypes.c_uint8), fp, ctypes.POINTER(i64),
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)], i),
+        "picp_batch_classify_time": ([vp, f, i, fp], i),
+        "picp_vo_set_track_stats": ([vp, i], i),
+        "picp_vo_get_map_stats": ([vp, i, i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(i64)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -309,6 +321,24 @@ class PICPSolver:
                                     ctypes.byref(st)))
         return {"H": H.reshape(6, 6).T.copy(), "b": b, **st.as_dict()}
 
+    def classify(self, correspondences):
+        """picp_classify at the current pose and kernel threshold: which correspondences the pose
+        rests on.  Returns dict(state (m,) uint8 CORR_*, chi2 (m,), uv (m, 2) (-1 where skipped),
+        inlier_idx (ascending correspondence indices of the inliers), counts (skipped, inlier,
+        outlier)).  Leaves the pose and the stats alone."""
+        self.set_correspondences(correspondences)
+        m = np.ascontiguousarray(correspondences, np.int32).reshape(-1, 2).shape[0]
+        state = np.zeros(max(m, 1), np.uint8)
+        chi2 = np.zeros(max(m, 1), np.float32)
+        uv = np.zeros(2 * max(m, 1), np.float32)
+        idx = np.zeros(max(m, 1), np.int32)
+        counts = np.zeros(3, np.int64)
+        _check(lib().picp_classify(self._h, self._threshold, state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                   _fptr(chi2), _fptr(uv), _i32ptr(idx),
+                                   counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return {"state": state[:m], "chi2": chi2[:m], "uv": uv[:2 * m].reshape(-1, 2),
+                "inlier_idx": idx[:int(counts[1])], "counts": counts}
+
 
 class Batch:
     """Independent PICP problems (frames) solved together on one device."""
@@ -367,6 +397,36 @@ class Batch:
 
     def sync(self):
         _check(lib().picp_batch_sync(self._b))
+
+    def classify(self, threshold, poses=None, want_chi2=True):
+        """picp_batch_classify at `poses` ((n, 4, 4) world-in-camera), or at the batch's current
+        poses (the last solve's, or those of a set_poses since).  Returns dict(state, chi2 (packed
+        order), inlier_off (n+1), inlier_idx (per problem ascending, relative to the problem's
+        first correspondence), counts (n, 3) skipped / inlier / outlier)."""
+        tot = int(self.offs[-1])
+        flat = None
+        if poses is not None:
+            Ts = np.asarray(poses, np.float32).reshape(self.n, 4, 4)
+            flat = np.ascontiguousarray(np.transpose(Ts, (0, 2, 1)).reshape(-1))
+        state = np.zeros(max(tot, 1), np.uint8)
+        chi2 = np.zeros(max(tot, 1), np.float32) if want_chi2 else None
+        idx = np.zeros(max(tot, 1), np.int32)
+        off = np.zeros(self.n + 1, np.int64)
+        counts = np.zeros(3 * self.n, np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(lib().picp_batch_classify(self._b, threshold, _fptr(flat) if flat is not None else None,
+                                         state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                         _fptr(chi2) if want_chi2 else None, off.ctypes.data_as(i64p),
+                                         _i32ptr(idx), counts.ctypes.data_as(i64p)))
+        return {"state": state[:tot], "chi2": chi2[:tot] if want_chi2 else None, "inlier_off": off,
+                "inlier_idx": idx[:int(off[-1])], "counts": counts.reshape(self.n, 3)}
+
+    def classify_time(self, threshold, reps):
+        """Mean device time (us) of one classify pass (kernels only) at the current poses, with
+        the outputs of the last classify() call."""
+        us = ctypes.c_float(0)
+        _check(lib().picp_batch_classify_time(self._b, threshold, reps, ctypes.byref(us)))
+        return us.value
 
     def time(self, reps, **params):
         """reps back-to-back solves between two HIP events -> (total ms, mean launch period us)."""
@@ -675,6 +735,21 @@ class VOSequence:
             out.append({k: v[o:o + st + 1] for k, v in recs.items()})
             o += st + 1
         return out
+
+    def track_stats(self, enable=True):
+        """Switch the per-map-point track counters (off by default); takes effect at the next run."""
+        _check(lib().picp_vo_set_track_stats(self._h, int(bool(enable))))
+
+    def map_stats(self, seg):
+        """(n_matched, n_inlier) per map point of segment seg after a run with tracking on:
+        accepted frame->map matches of the point, and those that are inliers at their step's final
+        PICP pose.  Raises PicpError(ERR_STATE) with tracking off."""
+        n = ctypes.c_int64()
+        _check(lib().picp_vo_get_map_stats(self._h, seg, 0, None, None, ctypes.byref(n)))
+        nm = np.zeros(max(n.value, 1), np.int32)
+        ni = np.zeros(max(n.value, 1), np.int32)
+        _check(lib().picp_vo_get_map_stats(self._h, seg, n.value, _i32ptr(nm), _i32ptr(ni), ctypes.byref(n)))
+        return nm[:n.value], ni[:n.value]
 
     def map(self, seg):
         n = ctypes.c_int64()

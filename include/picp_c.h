@@ -114,6 +114,26 @@ int picp_solve(picp_t* h, const picp_params* params, picp_stats* stats);
 int picp_linearize(picp_t* h, float threshold, int keep_outliers, double H[36], double b[6],
                    picp_stats* stats);
 
+/* ---------------- which correspondences a pose rests on (read-only observation) ---------------- */
+
+/* state of one correspondence at a pose (src/picp_solver.cpp:62-89) */
+#define PICP_CORR_SKIPPED 0  /* projectPoint returned false: the reference counts it nowhere */
+#define PICP_CORR_INLIER  1  /* projected and !(chi2 > threshold)  (strict gate, NaN passes) */
+#define PICP_CORR_OUTLIER 2  /* projected and chi2 > threshold                               */
+
+/* Classify the current correspondences (index k = correspondence k of picp_set_correspondences)
+ * at the handle's current pose (picp_get_pose), with the solve kernels' own projection, bounds
+ * test, error and chi2 (bit-identical to errorAndJacobian at that pose).  Needs points and
+ * correspondences set (PICP_ERR_STATE otherwise); m = 0 gives counts 0/0/0.  Blocking.  Changes
+ * neither the pose nor the stats nor the bits of a later solve.  Every output but counts may be
+ * NULL.  inlier_idx: only its first counts[1] entries are written. */
+int picp_classify(picp_t* h, float threshold,
+                  uint8_t* state,       /* m,   nullable */
+                  float* chi2,          /* m,   nullable; -1 where SKIPPED */
+                  float* proj_uv,       /* 2*m, nullable; (-1,-1) where SKIPPED (Camera::projectPoints' point_outside) */
+                  int32_t* inlier_idx,  /* m,   nullable; correspondence indices of the inliers, ascending */
+                  int64_t counts[3]);   /* required: number of SKIPPED / INLIER / OUTLIER */
+
 /* ---------------- batched independent problems (frames) on one device ---------------- */
 
 /* corr_offsets[n_problems+1]: problem i owns correspondences [off[i], off[i+1]) of the
@@ -130,6 +150,9 @@ int picp_batch_set_data(picp_batch_t* b, const float* xyz, const float* uv);
 int picp_batch_set_data_device(picp_batch_t* b, const float* d_x, const float* d_y,
                                const float* d_z, const float* d_u, const float* d_v);
 
+/* The initial poses of the following solves.  They also become the batch's current poses: what
+ * picp_batch_get_poses returns until the next solve completes (before, it returned the last
+ * solve's poses, or zeros before any solve); the stats are not touched. */
 int picp_batch_set_poses(picp_batch_t* b, const float* T_wc /* 16*n_problems */);
 int picp_batch_get_poses(picp_batch_t* b, float* T_wc /* 16*n_problems */);
 int picp_batch_get_stats(picp_batch_t* b, picp_stats* stats /* n_problems */);
@@ -161,6 +184,25 @@ int picp_batch_info(picp_batch_t* b, int64_t* total_corr, int* n_blocks, int* mo
  * used only when grid <= resident; if a hand-off wait still times out (CUs held by other work),
  * the solve is re-run without hand-offs and the batch keeps that layout: fallbacks counts it. */
 int picp_batch_residency(picp_batch_t* b, int* grid, int* resident, int* fallbacks);
+
+/* picp_classify for every problem of the batch in one pass (PICP_CORR_* per correspondence, in
+ * the caller's packed order).  T_wc: the poses to classify at, or NULL for the batch's current
+ * poses: what picp_batch_get_poses returns now, i.e. the last completed solve's results, or the
+ * poses of a picp_batch_set_poses made since (which that call now also reports).  inlier_idx
+ * holds, problem after problem, the ascending indices of each problem's inliers relative to its
+ * first correspondence: problem p's are inlier_idx[inlier_off[p] .. inlier_off[p+1]).  counts[3p
+ * .. 3p+2] = SKIPPED / INLIER / OUTLIER of problem p.  Blocking; read-only like picp_classify. */
+int picp_batch_classify(picp_batch_t* b, float threshold,
+                        const float* T_wc,    /* 16*n_problems, or NULL = what picp_batch_get_poses returns now */
+                        uint8_t* state, float* chi2,          /* total, caller's packed order (corr_offsets); nullable */
+                        int64_t* inlier_off,  /* n_problems+1, nullable */
+                        int32_t* inlier_idx,  /* total, nullable; per problem ascending, relative to the problem's first correspondence */
+                        int64_t* counts);     /* 3*n_problems, required */
+
+/* device time of one classify pass (kernels only, no copies), mean of reps; diagnostic.  The pass
+ * runs at the batch's current poses and writes what the batch's last picp_batch_classify asked
+ * for (state and the inlier indices always; chi2 if that call passed a chi2 array). */
+int picp_batch_classify_time(picp_batch_t* b, float threshold, int reps, float* us_per_pass);
 
 /* ---------------- batch split across GPUs: one process per GPU ---------------- */
 
@@ -321,6 +363,20 @@ int picp_vo_get_poses(picp_vo_t* h, float* poses);
 int picp_vo_get_steps(picp_vo_t* h, picp_vo_step* steps);
 /* segment map: *n = its size; the first min(n, cap) points are copied to xyz / desc (nullable) */
 int picp_vo_get_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, float* desc, int64_t* n);
+/* Per-map-point track counters, off by default; read-only (poses, step records and maps keep
+ * their bits).  May be switched any time before a run; the counters are zeroed at the start of
+ * every run.  After a run, for map point j of segment seg:
+ *   n_matched[j] = accepted frame->map matches whose best index was j, over the segment's steps;
+ *   n_inlier[j]  = those of them that are PICP_CORR_INLIER, at the segment parameters' threshold,
+ *                  at the step's FINAL PICP pose (the pose after the last update, world-in-camera:
+ *                  the one picp_vo_get_poses reports inverted).  picp_vo_step.n_in counts the
+ *                  inliers of the last LINEARISATION point instead, one update earlier, so the
+ *                  sum of n_inlier over a step's matches need not equal its n_in.
+ * picp_vo_get_map_stats: *n = the segment's map size; the first min(n, cap) entries are copied
+ * (n_matched / n_inlier nullable), as in picp_vo_get_map.  PICP_ERR_STATE with tracking off. */
+int picp_vo_set_track_stats(picp_vo_t* h, int enable);
+int picp_vo_get_map_stats(picp_vo_t* h, int seg, int64_t cap,
+                          int32_t* n_matched, int32_t* n_inlier, int64_t* n);
 /* mean device time of `reps` back-to-back runs (HIP events on the handle's stream) */
 int picp_vo_time(picp_vo_t* h, int reps, float* ms_per_run);
 int picp_vo_info(picp_vo_t* h, int64_t* n_obs, int64_t* n_slots, int64_t* map_slots, int* npt);

@@ -18,6 +18,7 @@
 #pragma once
 #include <cstdint>
 #include <iostream>
+#include <vector>
 
 #include "picp_c.h"
 #include "pr/camera.h"
@@ -126,6 +127,27 @@ class PICPSolver {
     if (converged) *converged = _stats.converged != 0;
     return _stats.rounds;
   }
+  //! which correspondences the current pose rests on (picp_classify, at kernelThreshold()):
+  //! state[k] = PICP_CORR_SKIPPED / _INLIER / _OUTLIER of correspondences[k], chi2[k] its chi2
+  //! (-1 where skipped).  The pose, the stats and later rounds are untouched.
+  bool classify(const IntPairVector& correspondences, std::vector<uint8_t>& state,
+                std::vector<float>* chi2 = nullptr) {
+    state.assign(correspondences.size(), 0);
+    if (chi2) chi2->assign(correspondences.size(), -1.0f);
+    int64_t counts[3];
+    return classify_raw(correspondences, state.data(), chi2 ? chi2->data() : nullptr, nullptr, counts);
+  }
+  //! the inlier pairs at the current pose, in correspondence order; returns their count
+  //! (-1 on error)
+  int inliers(const IntPairVector& correspondences, IntPairVector& out) {
+    std::vector<int32_t> idx(correspondences.size());
+    int64_t counts[3];
+    out.clear();
+    if (!classify_raw(correspondences, nullptr, nullptr, idx.data(), counts)) return -1;
+    out.reserve((size_t)counts[1]);
+    for (int64_t k = 0; k < counts[1]; ++k) out.push_back(correspondences[(size_t)idx[(size_t)k]]);
+    return (int)counts[1];
+  }
   void setDamping(float d) { _damping = d; }
   void setMinNumInliers(int n) { _min_num_inliers = n; }
   int lastStatus() const { return _status; }
@@ -139,6 +161,16 @@ class PICPSolver {
       return false;
     }
     return true;
+  }
+  bool classify_raw(const IntPairVector& correspondences, uint8_t* state, float* chi2, int32_t* idx,
+                    int64_t counts[3]) {
+    counts[0] = counts[1] = counts[2] = 0;
+    if (!_h) return false;
+    if (!check(picp_set_correspondences(_h, reinterpret_cast<const int32_t*>(correspondences.data()),
+                                        (int64_t)correspondences.size()),
+               "picp_set_correspondences"))
+      return false;
+    return check(picp_classify(_h, _kernel_thereshold, state, chi2, nullptr, idx, counts), "picp_classify");
   }
   void pull_pose() {
     float T[16];
