@@ -76,6 +76,26 @@ struct ClsArgs {
   int32_t pinhole;     // 1: the pinhole-K operation order (accumulate_pinhole), 0: general K
 };
 
+// point refinement (picp_refine.hip): camera, gate and loop parameters, by value
+struct RefineArgs {
+  float K[9];            // camera matrix, column-major
+  float maxx, maxy;      // cols-1, rows-1
+  float threshold;       // chi2 gate
+  float damping;
+  float conv_eps;        // negative: never converge
+  int32_t min_inliers;
+  int32_t keep_outliers;
+  int32_t max_rounds;
+  int32_t pinhole;       // set by the launcher (classify_item's camera path)
+  int64_t n_points;
+};
+
+// one world-in-camera pose of the refiner's table: the rows of [R | t], 48 B (three 16-B loads)
+struct RefinePose {
+  float4 r0, r1, r2;     // (r00 r01 r02 t0), (r10 r11 r12 t1), (r20 r21 r22 t2)
+};
+
+static_assert(sizeof(RefinePose) == 48, "RefinePose must be 48 B");
 static_assert(sizeof(PicpState) == 128, "PicpState must be 128 B");
 static_assert(sizeof(PicpProblem) % 8 == 0, "PicpProblem alignment");
 

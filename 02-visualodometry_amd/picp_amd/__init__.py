@@ -49,6 +49,9 @@ EXPORTED = [
     "picp_comm_allreduce_max", "picp_comm_barrier", "picp_batch_allgather", "picp_batch_allgather_host",
     "picp_classify", "picp_batch_classify", "picp_batch_classify_time",
     "picp_vo_set_track_stats", "picp_vo_get_map_stats",
+    "picp_refine_params_default", "picp_refine_create", "picp_refine_destroy", "picp_refine_set_poses",
+    "picp_refine_set_tracks", "picp_refine_set_points", "picp_refine_run", "picp_refine_get_points",
+    "picp_refine_get_stats", "picp_refine_time",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -177,6 +180,16 @@ def lib():
         "picp_vo_set_track_stats": ([vp, i], i),
         "picp_vo_get_map_stats": ([vp, i, i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                    ctypes.POINTER(i64)], i),
+        "picp_refine_params_default": ([pp], None),
+        "picp_refine_create": ([ctypes.POINTER(vp), i, i, i, fp], i),
+        "picp_refine_destroy": ([vp], i),
+        "picp_refine_set_poses": ([vp, fp, i], i),
+        "picp_refine_set_tracks": ([vp, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32), fp], i),
+        "picp_refine_set_points": ([vp, fp], i),
+        "picp_refine_run": ([vp, pp], i),
+        "picp_refine_get_points": ([vp, fp], i),
+        "picp_refine_get_stats": ([vp, sp], i),
+        "picp_refine_time": ([vp, pp, i, fp], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -758,6 +771,101 @@ class VOSequence:
         desc = np.zeros(max(n.value, 1) * self.dim, np.float32)
         _check(lib().picp_vo_get_map(self._h, seg, n.value, _fptr(xyz), _fptr(desc), ctypes.byref(n)))
         return xyz[:3 * n.value].reshape(-1, 3), desc[:self.dim * n.value].reshape(-1, self.dim)
+
+
+def default_refine_params(**kw):
+    """picp_refine_params (the same layout as picp_params): threshold 3000, damping 1, min_inliers 2,
+    keep_outliers 0, max_rounds 10, conv_eps 1e-5."""
+    p = Params()
+    lib().picp_refine_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class PointRefiner:
+    """picp_refine_t: refine map points against all of their observations with the poses held
+    fixed (structure-only Gauss-Newton, csrc/picp_refine.hip).  Poses, tracks and points stay on
+    the device between calls."""
+
+    def __init__(self, device=0, rows=480, cols=640, K=K_REF):
+        self._h = ctypes.c_void_p()
+        self.device = device
+        self.n_points = None
+        _check(lib().picp_refine_create(ctypes.byref(self._h), device, rows, cols, _fptr(k_to_c(K))))
+
+    def close(self):
+        if self._h:
+            lib().picp_refine_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_poses(self, Ts):
+        """(n, 4, 4) world-in-camera poses."""
+        Ts = np.asarray(Ts, np.float32).reshape(-1, 4, 4)
+        flat = np.ascontiguousarray(np.transpose(Ts, (0, 2, 1)).reshape(-1))
+        _check(lib().picp_refine_set_poses(self._h, _fptr(flat) if flat.size else None, Ts.shape[0]))
+
+    def set_tracks(self, track_off, obs_pose, obs_uv):
+        """CSR tracks: point i owns observations [track_off[i], track_off[i+1]) of obs_pose (pose
+        indices) and obs_uv ((n_obs, 2) pixels)."""
+        off = np.ascontiguousarray(track_off, np.int64)
+        op = np.ascontiguousarray(obs_pose, np.int32).reshape(-1)
+        uv = _f32(obs_uv, (-1,))
+        assert off.size >= 1 and uv.size == 2 * op.size
+        _check(lib().picp_refine_set_tracks(self._h, off.size - 1, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                            _i32ptr(op) if op.size else None, _fptr(uv) if uv.size else None))
+        self.n_points = off.size - 1
+
+    def set_points(self, xyz):
+        xyz = _f32(xyz, (-1,))
+        assert self.n_points is None or xyz.size == 3 * self.n_points
+        _check(lib().picp_refine_set_points(self._h, _fptr(xyz) if xyz.size else None))
+
+    def points(self):
+        n = self.n_points or 0
+        out = np.zeros((n, 3), np.float32)
+        _check(lib().picp_refine_get_points(self._h, _fptr(out) if n else None))
+        return out
+
+    def stats(self):
+        """dict of per-point arrays: chi_in, chi_out, n_in, ok, rounds, converged, n_projected."""
+        n = self.n_points or 0
+        st = (Stats * max(n, 1))()
+        _check(lib().picp_refine_get_stats(self._h, st))
+        rec = np.frombuffer(st, dtype=np.dtype([(k, np.float32 if t is ctypes.c_float else np.int32)
+                                                for k, t in Stats._fields_]), count=n)
+        return {k: rec[k].copy() for k, _ in Stats._fields_ if k != "reserved"}
+
+    def run(self, **params):
+        """Refine the current points in place -> (xyz (n, 3), stats)."""
+        prm = default_refine_params(**params)
+        _check(lib().picp_refine_run(self._h, ctypes.byref(prm)))
+        return self.points(), self.stats()
+
+    def time(self, reps, **params):
+        """Mean device time (us) of one run; the points are restored before every repetition."""
+        prm = default_refine_params(**params)
+        us = ctypes.c_float(0)
+        _check(lib().picp_refine_time(self._h, ctypes.byref(prm), reps, ctypes.byref(us)))
+        return us.value
+
+
+def refine_points(K, rows, cols, poses, track_off, obs_pose, obs_uv, xyz, device=0, **params):
+    """One-shot PointRefiner: -> (refined xyz (n, 3), stats)."""
+    r = PointRefiner(device=device, rows=rows, cols=cols, K=K)
+    try:
+        r.set_poses(poses)
+        r.set_tracks(track_off, obs_pose, obs_uv)
+        r.set_points(xyz)
+        return r.run(**params)
+    finally:
+        r.close()
 
 
 def selftest_rcp(e_lo=-8, e_hi=8, device=0):

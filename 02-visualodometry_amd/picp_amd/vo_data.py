@@ -73,6 +73,22 @@ class VOData:
         pairs = [(i, self._id2row[int(r)]) for i, r in enumerate(f["id_real"]) if int(r) in self._id2row]
         return np.array(pairs, np.int32).reshape(-1, 2)
 
+    def tracks(self, min_obs=2):
+        """CSR tracks of world.dat's landmarks by id_real: (rows, track_off, obs_pose, obs_uv) --
+        the world rows kept (those with at least min_obs observations, ascending), track_off
+        (len(rows) + 1, int64), and per observation the frame index (int32: an index into the
+        per-frame poses) and the pixel, each track sorted by frame."""
+        row = np.array([self._id2row.get(int(r), -1) for r in self.meas_real], np.int64)
+        sel = np.nonzero(row >= 0)[0]
+        order = sel[np.lexsort((self.meas_id[sel], self.meas_frame[sel], row[sel]))]
+        count = np.bincount(row[order], minlength=len(self.world_id))
+        rows = np.nonzero(count >= max(int(min_obs), 0))[0]
+        keep = order[np.isin(row[order], rows)]
+        off = np.zeros(len(rows) + 1, np.int64)
+        off[1:] = np.cumsum(count[rows])
+        return (rows, off, np.ascontiguousarray(self.meas_frame[keep], np.int32),
+                np.ascontiguousarray(self.meas_uv[keep], np.float32))
+
     def packed(self):
         """The 121 frames packed for the VO sequence APIs: (frame_off int64, uv, desc)."""
         order = np.lexsort((self.meas_id, self.meas_frame))

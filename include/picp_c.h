@@ -265,6 +265,62 @@ int picp_triangulate(int device, const float P1[12], const float P2[12], const f
 /* Helper: P = K * inverse(T_cw)(0:3,0:4) from a camera-in-world pose (src/cam.cpp:109-112). */
 int picp_projection_matrix(const float K[9], const float T_cw[16], float P[12]);
 
+/* ---------------- multi-view refinement of map points (structure-only Gauss-Newton) ---------------- */
+
+/* Refine 3-D points against ALL of their observations with the poses held fixed: the structure-only
+ * counterpart of picp_solve (the same projection, bounds test, strict chi2 gate, robust weight and
+ * damped Gauss-Newton; a 3x3 system per point).  Alternated with the pose solves it is a bundle
+ * adjustment; on its own it is N-view triangulation.
+ *
+ * Per point X, independently, for up to max_rounds rounds:
+ *   accumulate over the point's observations (k, uv) in track order: pc = R_k X + t_k; skipped
+ *     (counted nowhere) if pc.z <= 0 or the projection leaves [0, cols-1] x [0, rows-1]; else
+ *     n_projected++, e = proj - uv, chi = e.e; chi > threshold: lambda = sqrt(threshold / chi),
+ *     chi_out += chi; else lambda = 1, chi_in += chi, n_in++; inliers (and outliers with
+ *     keep_outliers) add H += J^T J lambda, b += J^T e lambda with J = Jp K R_k (2x3);
+ *   the recorded stats are those of this linearisation, before the update (as in picp_solve);
+ *   n_in < min_inliers: ok = 0, the point keeps its value and stops;
+ *   H += damping I, solve H dx = -b; H not positive definite or dx not finite: ok = 0, the point
+ *     keeps its value and stops; else X += dx, rounds++;
+ *   picp_solve's convergence rule on chi_in (conv_eps < 0 disables it).
+ * All rounds of all points run in one launch; results are bit-reproducible from run to run. */
+typedef struct picp_refine picp_refine_t;
+
+typedef struct picp_refine_params {
+  float threshold;       /* chi2 gate, 3000 (exec/icp_test.cpp:86)                       */
+  float damping;         /* 1                                                            */
+  int32_t min_inliers;   /* 2: one view does not fix a point                             */
+  int32_t keep_outliers; /* 0                                                            */
+  int32_t max_rounds;    /* 10                                                           */
+  float conv_eps;        /* 1e-5 relative chi_in change; < 0 disables                    */
+} picp_refine_params;
+
+void picp_refine_params_default(picp_refine_params* p);
+int picp_refine_create(picp_refine_t** out, int device, int rows, int cols, const float K[9]);
+int picp_refine_destroy(picp_refine_t* h);
+/* World-in-camera poses, 16 floats each, column-major as for picp_set_pose.  Copied. */
+int picp_refine_set_poses(picp_refine_t* h, const float* T_wc /* 16*n_poses */, int n_poses);
+/* Tracks in CSR form: point i owns observations [track_off[i], track_off[i+1]) of obs_pose (an
+ * index into the poses) and obs_uv (float2 pixels).  track_off[0] must be 0, the offsets must not
+ * decrease and their end must fit an int32 (PICP_ERR_ARG); a pose index outside [0, n_poses) is
+ * PICP_ERR_RANGE (checked at picp_refine_run when the poses are set after the tracks).  Copied.
+ * Changing n_points drops the points (set them again). */
+int picp_refine_set_tracks(picp_refine_t* h, int64_t n_points, const int64_t* track_off,
+                           const int32_t* obs_pose, const float* obs_uv);
+int picp_refine_set_points(picp_refine_t* h, const float* xyz /* 3*n_points */);
+/* Refines the current points in place (a second run continues from the first's result).
+ * PICP_ERR_STATE before poses, tracks or points were set.  n_points == 0 launches nothing.
+ * Blocking. */
+int picp_refine_run(picp_refine_t* h, const picp_refine_params* params);
+int picp_refine_get_points(picp_refine_t* h, float* xyz /* 3*n_points */);
+/* Per point: the stats of its last linearisation, ok, rounds (updates applied), converged. */
+int picp_refine_get_stats(picp_refine_t* h, picp_stats* stats /* n_points */);
+/* Mean device time of one run over `reps` runs (HIP events around the kernel launches only).  The
+ * points are restored before every repetition (outside the timed spans), so every repetition does
+ * the same work; afterwards the points and stats are those of one run from the points the call
+ * found. */
+int picp_refine_time(picp_refine_t* h, const picp_refine_params* params, int reps, float* us_per_run);
+
 /* ---------------- descriptor matching (match_points replacement) ---------------- */
 
 /* src/my_utilities.h:70-120: for each of the n1 descriptors of set 1 (float[dim], packed) the
