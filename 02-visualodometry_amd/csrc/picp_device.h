@@ -1061,6 +1061,13 @@ __device__ __forceinline__ double tri_rsq(double x) {
 // (Hestenes) Jacobi, at most 10 sweeps, stopping after the first sweep that rotates nothing
 // (every later sweep would be a no-op); all indices compile-time so A and V stay in registers.
 // A is consumed.
+// A with a non-finite entry gives four NaNs.  Left alone it would give a finite vector: a column
+// with a NaN or Inf entry keeps one through every rotation (c x - s y of a non-finite x is
+// non-finite), its products gamma are NaN or Inf and fail the rotation test (NaN compares false,
+// Inf > Inf is false), its norm never compares below `best`, and so the result would be another
+// column of V, or column 0 of the identity when every column is affected (a NaN pixel: the finite
+// point (1, 0, 0)).  A finite A keeps finite norms (entries below 2^257), so the sum of the four
+// norms is finite exactly then.
 __device__ __forceinline__ void tri_null_jacobi(double A[4][4], double v[4]) {
   double Vm[4][4];
 #pragma unroll
@@ -1114,6 +1121,9 @@ __device__ __forceinline__ void tri_null_jacobi(double A[4][4], double v[4]) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = take ? Vm[r][c] : v[r];
   }
+  const bool finite = (nrm[0] + nrm[1]) + (nrm[2] + nrm[3]) <= DBL_MAX;  // false for NaN and Inf
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = finite ? v[r] : __builtin_nan("");
 }
 
 // Two-view linear (DLT) triangulation of one point, cv::triangulatePoints as called from
@@ -1121,6 +1131,9 @@ __device__ __forceinline__ void tri_null_jacobi(double A[4][4], double v[4]) {
 // A (4x4) in double; X_h = the right singular vector of A's smallest singular value, by the
 // one-sided Jacobi above (tri_null_jacobi).  (Inverse iteration on A^T A was slower: DESIGN.md
 // Appendix A, "inverse-iteration triangulation".)
+// A non-finite pixel or P entry gives (NaN, NaN, NaN), as OpenCV's SVD does (tri_null_jacobi's
+// rule: every input reaches an entry of A, a product of floats in double cannot overflow and
+// 0 * Inf is NaN, so A is finite exactly when the inputs are; a NaN W4 selects scale 1).
 __device__ inline void triangulate_dlt(const float* P1, const float* P2, float2 a, float2 b,
                                        float out[3]) {
   double A[4][4];

@@ -704,22 +704,37 @@ extern "C" __global__ __launch_bounds__(ESS_BLOCK) void picp_ess_pose_kernel(
 // ------------------------------- host launch wrapper -------------------------------
 // Buffers (device): offs n_problems+1; p1/p2 float pixel pairs; idx 5*max_iters per problem;
 // Es 90*max_iters doubles per problem; ns max_iters per problem; cnt 10*max_iters per problem.
+// The hypothesis and score kernels take the problem from blockIdx.y, so a batch runs in slices of
+// at most ESS_MAX_GRID_Y problems (the y limit of a grid): the per-problem arrays are shifted by
+// the slice start; p1, p2 and mask are indexed through the absolute offsets and are not.
+#define ESS_MAX_GRID_Y 65535
 extern "C" hipError_t picp_launch_essential(hipStream_t stream, const EssArgs* args, const int64_t* offs,
                                            const float* p1, const float* p2, int32_t* idx, double* Es,
                                            int32_t* ns, int32_t* cnt, float* T_out, int32_t* inliers,
                                            int32_t* good, uint8_t* mask) {
   if (!args || args->n_problems <= 0 || args->max_iters <= 0) return hipErrorInvalidValue;
-  const EssArgs A = *args;
   hipError_t e;
-  hipLaunchKernelGGL(picp_ess_samples_kernel, dim3((A.n_problems + 63) / 64), dim3(64), 0, stream, A, offs, idx);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(picp_ess_hyp_kernel, dim3((A.max_iters + 63) / 64, A.n_problems), dim3(64), 0, stream, A, offs,
-                     p1, p2, idx, Es, ns);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(picp_ess_score_kernel, dim3(A.max_iters, A.n_problems), dim3(64), 0, stream, A, offs, p1, p2,
-                     Es, ns, cnt);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(picp_ess_pose_kernel, dim3(A.n_problems), dim3(ESS_BLOCK), 0, stream, A, offs, p1, p2, Es, ns,
-                     cnt, T_out, inliers, good, mask);
-  return hipGetLastError();
+  for (int s0 = 0; s0 < args->n_problems; s0 += ESS_MAX_GRID_Y) {
+    EssArgs A = *args;
+    A.n_problems = (args->n_problems - s0 < ESS_MAX_GRID_Y) ? args->n_problems - s0 : ESS_MAX_GRID_Y;
+    const size_t h0 = (size_t)s0 * A.max_iters;  // first (problem, hypothesis) of the slice
+    const int64_t* s_offs = offs + s0;
+    int32_t* s_idx = idx + h0 * 5;
+    double* s_Es = Es + h0 * 90;
+    int32_t* s_ns = ns + h0;
+    int32_t* s_cnt = cnt + h0 * 10;
+    hipLaunchKernelGGL(picp_ess_samples_kernel, dim3((A.n_problems + 63) / 64), dim3(64), 0, stream, A, s_offs,
+                       s_idx);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(picp_ess_hyp_kernel, dim3((A.max_iters + 63) / 64, A.n_problems), dim3(64), 0, stream, A,
+                       s_offs, p1, p2, s_idx, s_Es, s_ns);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(picp_ess_score_kernel, dim3(A.max_iters, A.n_problems), dim3(64), 0, stream, A, s_offs, p1,
+                       p2, s_Es, s_ns, s_cnt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(picp_ess_pose_kernel, dim3(A.n_problems), dim3(ESS_BLOCK), 0, stream, A, s_offs, p1, p2,
+                       s_Es, s_ns, s_cnt, T_out + (size_t)16 * s0, inliers + s0, good + s0, mask);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
 }

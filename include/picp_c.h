@@ -259,7 +259,11 @@ int picp_batch_allgather_host(picp_batch_t* b, int world, int rank, picp_exchang
 /* ---------------- linear triangulation (cv::triangulatePoints replacement) ---------------- */
 
 /* src/cam.cpp:94-140: per point DLT with two 3x4 row-major projection matrices, then
- * dehomogenisation.  uv1/uv2: float[2*q]; xyz_out: float[3*q].  Host pointers. */
+ * dehomogenisation.  uv1/uv2: float[2*q]; xyz_out: float[3*q].  Host pointers.
+ * A point with a non-finite (NaN or Inf) pixel coordinate in either view comes out as three NaNs,
+ * and every point does when P1 or P2 has a non-finite entry (cv::triangulatePoints gives NaN
+ * there too); the other points of the call are not affected.  The VO sequence's bootstrap and
+ * append steps triangulate by the same rule. */
 int picp_triangulate(int device, const float P1[12], const float P2[12], const float* uv1,
                      const float* uv2, int64_t q, float* xyz_out);
 /* Helper: P = K * inverse(T_cw)(0:3,0:4) from a camera-in-world pose (src/cam.cpp:109-112). */
@@ -372,7 +376,8 @@ void picp_essential_params_default(picp_essential_params* p);
  * camera-in-world pose of the second view with the first at the origin, [R | t]^-1 column-major
  * (Cam::getPose, src/cam.cpp:81,227; unit baseline), inliers = findEssentialMat's inlier count
  * (0: no model, T = I), good = recoverPose's count.  mask (may be NULL): offs[n] bytes, 1 for
- * the points recoverPose keeps. */
+ * the points recoverPose keeps.  Any n_problems >= 1: batches above 65535 problems run in slices
+ * of 65535 on the device, inside the one call. */
 int picp_essential_batch(int device, int n_problems, const int64_t* offs, const float* p1,
                          const float* p2, const float K[9], const picp_essential_params* prm,
                          float* T_out, int32_t* inliers, int32_t* good, uint8_t* mask);

@@ -14,7 +14,16 @@ What is compared, and how strictly:
       pose      : se3_log_norm(gpu, oracle) < 1e-4 (BASELINE.json north_star tolerance)
       new points: |gpu - oracle| <= 1e-4 * (1 + |oracle|) for 99% of points, all within 1e-2
                   relative (low-parallax points near the epipole are ill-conditioned; the two
-                  sides use different SVD methods)
+                  sides use different SVD methods);
+                  and EVERY bootstrap and appended point, whatever its conditioning, is held to
+                  the residual bound of tests/tri_reference.py against a float64 SVD of its own
+                  DLT matrix A (from oracle.projection_matrix of the GPU's poses and the pixel
+                  pair that produced it): |A xh| <= sigma4 + 8 EPS32 sigma1.  The constant is 8
+                  where picp_triangulate's is 4: the device forms P itself and its entries may
+                  differ from the host's by one float ulp, |dA|_F <= EPS32 |A|_F <= 2 EPS32 sigma1
+                  on top of the 2.5 EPS32 of the result's own roundings.  Worst ratio observed
+                  on an MI355X over the tests of this module: 0.51 (synthetic segments, a
+                  bootstrap point; data/: 0.10)
   * the free-running sequence is chaotic (a 1e-7 difference in one step grows through the
     triangulated map; the oracle's own float32-vs-float64 accumulation modes drift apart by
     2.4e-3 over data/), so whole-trajectory agreement is a loose band only (2e-2).
@@ -22,10 +31,25 @@ What is compared, and how strictly:
 import numpy as np
 import pytest
 
+import tri_reference as TR
+
 pytestmark = pytest.mark.gpu
 
 POSE_TOL = 1e-4
 THR = 3000.0
+VO_RES_C = 8.0
+
+
+def _assert_tri_residual(P1, P2, uva, uvb, got, what):
+    """Bound (a) of tests/tri_reference.py with the constant 8, on every point; returns the worst ratio."""
+    if len(got) == 0:
+        return 0.0
+    assert np.isfinite(got).all(), what
+    ref = TR.reference(P1, P2, uva, uvb)
+    res = TR.residual_ratio(ref, got)
+    k = int(np.argmax(res))
+    assert res[k] <= VO_RES_C, "%s: residual ratio %.3g at point %d (kappa %.3g)" % (what, res[k], k, ref["kappa"][k])
+    return float(res[k])
 
 
 def _se3(a, b):
@@ -58,6 +82,8 @@ def _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, map_xyz, map_desc)
             P1 = oracle.projection_matrix(K, poses[t])
             P2 = oracle.projection_matrix(K, poses[t + 1])
             X = oracle.triangulate(P1, P2, uv[off[cf]:off[cf + 1]][ia], uv[off[nf]:off[nf + 1]][ib])
+            _assert_tri_residual(P1, P2, uv[off[cf]:off[cf + 1]][ia], uv[off[nf]:off[nf + 1]][ib],
+                                 map_xyz[m:m + len(ia)], "segment at frame %d, step %d" % (f0, t))
             tri_err.append(np.abs(map_xyz[m:m + len(ia)] - X).max(1))
             tri_ref.append(1.0 + np.abs(X).max(1))
         m += len(ia)
@@ -74,8 +100,12 @@ def _check_segment(oracle, K, off, uv, desc, f0, T0, T1, poses, rec, mx, md):
     X = oracle.triangulate(oracle.projection_matrix(K, T0), oracle.projection_matrix(K, T1),
                            uv[off[f0]:off[f0 + 1]][ia], uv[off[f0 + 1]:off[f0 + 2]][pm["best_idx"][ia]])
     np.testing.assert_allclose(mx[:len(ia)], X, rtol=1e-4, atol=1e-4)
+    _assert_tri_residual(oracle.projection_matrix(K, T0), oracle.projection_matrix(K, T1), uv[off[f0]:off[f0 + 1]][ia],
+                         uv[off[f0 + 1]:off[f0 + 2]][pm["best_idx"][ia]], mx[:len(ia)],
+                         "segment at frame %d, bootstrap" % f0)
     np.testing.assert_array_equal(poses[0], np.asarray(T0, np.float32))
     worst, rel = _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, mx, md)
+    print("VO_TRI segment at frame %d: %d map points inside the residual bound" % (f0, len(mx)))
     assert worst < POSE_TOL, worst
     assert np.quantile(rel, 0.99) < 1e-4 and rel.max() < 1e-2, (np.quantile(rel, 0.99), rel.max())
 
