@@ -224,6 +224,10 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
   __shared__ int s_done;
   __shared__ int s_tmo;  // a partner wait timed out (the error word is for the host)
   __shared__ PicpState s_st;
+  // total_word's per-lane constants: in LDS, read each round with the combine's loads (24 bytes
+  // per lane at a 24-byte stride: 8-byte-aligned loads, landing with the eight s_wave words), not
+  // in registers across the linearize: the 128-VGPR split-4 variants have none to spare
+  __shared__ __attribute__((aligned(16))) TotalLane s_tl[PICP_NPART];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int p = blockIdx.x, h = 0;
@@ -309,6 +313,7 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
     s_tmo = 0;
     s_st = s;
   }
+  if (tid < PICP_NPART) s_tl[tid] = total_lane(A, tid);
   __syncthreads();
 
   Cam C;
@@ -397,6 +402,7 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
       float ws[BS / 64];  // every load issued before the first add (one LDS wait)
 #pragma unroll
       for (int w = 0; w < BS / 64; ++w) ws[w] = s_wave[tid][w];
+      const TotalLane tl = s_tl[tid];
       double t = (double)ws[0];
 #pragma unroll
       for (int w = 1; w < BS / 64; ++w) t += (double)ws[w];
@@ -454,7 +460,7 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
         for (int q = 1; q < 4; ++q)
           if (q < split) t += part_t[q];
       }
-      s_tot[tid] = total_word(A, tid, t);  // lane e converts total e
+      s_tot[tid] = total_word(tl, t);  // lane e converts total e (tid < 32: the lane)
     }
     // the totals (and s_tmo) were written by lanes < 32 of wave 0, which also runs the solve:
     // a wave barrier orders them, the other waves wait at the block barrier after the solve

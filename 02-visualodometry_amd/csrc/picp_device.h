@@ -813,6 +813,29 @@ __device__ __forceinline__ float wave_reduce32(float* v, int lane) {
   return v[0] + dpp<DPP_QUAD_XOR1>(v[0]);
 }
 
+// x + (x of the lane 16, or 32, away) for a double, through the swaps of wave_reduce32 on its two
+// halves (no LDS round trip, unlike __shfl_xor's ds_bpermute).  With both operands x, the swap
+// leaves (own, partner) in one half of the pair and (partner, own) in the other: the sum is
+// own + partner or partner + own, the same bits (IEEE addition commutes).
+template <int DIST>
+__device__ __forceinline__ double wave_add_xor_f64(double x) {
+  static_assert(DIST == 16 || DIST == 32, "the two swap distances");
+  const unsigned lo = (unsigned)__double_as_longlong(x), hi = (unsigned)(__double_as_longlong(x) >> 32);
+  unsigned a_lo, a_hi, b_lo, b_hi;
+  if constexpr (DIST == 16) {
+    const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    a_lo = rl[0]; b_lo = rl[1]; a_hi = rh[0]; b_hi = rh[1];
+  } else {
+    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    a_lo = rl[0]; b_lo = rl[1]; a_hi = rh[0]; b_hi = rh[1];
+  }
+  const double a = __longlong_as_double((long long)(((unsigned long long)a_hi << 32) | a_lo));
+  const double b = __longlong_as_double((long long)(((unsigned long long)b_hi << 32) | b_lo));
+  return a + b;
+}
+
 // 1/d in float: hardware v_rcp_f32 estimate refined by one Newton step (<= 1 ulp for normal
 // d); |d| <= FLT_MIN -> 0 (Eigen's LDLT zero-pivot rule for float, src/picp_solver.cpp:102).
 __device__ __forceinline__ float rcp32(float d) {
@@ -953,6 +976,40 @@ __device__ __forceinline__ float total_word(const PicpArgs& A, int e, double t) 
   const float f = (float)d;
   const float c = __int_as_float((int32_t)t);
   return (e < PICP_P_N_IN) ? f : ((e < 31) ? c : 0.0f);
+}
+
+// total_word for a lane that converts the same total e every round (the finishing wave of the
+// persistent and block kernels): what depends on e only, computed once per launch (the
+// persistent kernel keeps it in VGPRs, the block kernel in LDS), so the round pays one add, the
+// two converts and four bit operations instead of the classification of e (compares, lane masks
+// in SGPR pairs).  20 bytes, 24 with the double's alignment.
+//   add   : (double)damping on the diagonal of H, +0.0 on the rest of H (total_word's t + 0.0),
+//           -0.0 elsewhere (t + -0.0 is t for every t, -0.0 included)
+//   sign  : the sign bit for -b.  Negating the float after the conversion gives the bits of
+//           converting -t: round-to-nearest is symmetric
+//   fmask / imask : all ones where the word is the float / the int conversion (both zero: word 31)
+struct TotalLane {
+  double add;
+  unsigned sign, fmask, imask;
+};
+
+__device__ __forceinline__ TotalLane total_lane(const PicpArgs& A, int e) {
+  const bool diag = (e == 0) | (e == 6) | (e == 11) | (e == 15) | (e == 18) | (e == 20);
+  TotalLane k;
+  k.add = diag ? (double)A.damping : ((e < PICP_P_B) ? 0.0 : -0.0);
+  k.sign = (e >= PICP_P_B && e < PICP_P_CHI_IN) ? 0x80000000u : 0u;
+  k.fmask = (e < PICP_P_N_IN) ? ~0u : 0u;
+  k.imask = (e >= PICP_P_N_IN && e < 31) ? ~0u : 0u;
+  // opaque from here: as plain selects of e the compiler turns the masks back into compares whose
+  // lane masks it hoists into (spilled) SGPR pairs
+  asm volatile("" : "+v"(k.add), "+v"(k.sign), "+v"(k.fmask), "+v"(k.imask));
+  return k;
+}
+
+__device__ __forceinline__ float total_word(const TotalLane& k, double t) {
+  const unsigned f = __float_as_uint((float)(t + k.add)) ^ k.sign;
+  const unsigned c = (unsigned)(int32_t)t;
+  return __uint_as_float((f & k.fmask) | (c & k.imask));
 }
 
 // What a round leaves besides the pose: the state fields no later round reads.

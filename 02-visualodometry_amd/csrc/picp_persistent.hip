@@ -87,6 +87,26 @@ __device__ __forceinline__ unsigned long long granule(unsigned epoch, float v) {
   return ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v);
 }
 
+// Word (lane & 15) of 16 words that every lane holds: four levels of bit selects on the lane id
+// (a v_bfe_i32 mask and 8, 4, 2, 1 v_bfi_b32).  No lane mask in an SGPR pair: the fourteen
+// (lane == i) selects this replaces kept theirs across the round loop, spilled, and reloaded each
+// (two v_readlane_b32 and an s_nop) in front of the pose stores.  The masks come from inline
+// assembly so that they are made where they are used (as plain C they are hoisted out of the
+// round loop into four VGPRs) and the selects are not turned back into compares.
+__device__ __forceinline__ unsigned lane_word16(const unsigned (&w)[16], int lane) {
+  unsigned v[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) v[k] = w[k];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    unsigned m;  // bit b of the lane in every bit
+    asm volatile("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(lane), "n"(b));
+#pragma unroll
+    for (int k = 0; k < (8 >> b); ++k) v[k] = (v[2 * k + 1] & m) | (v[2 * k] & ~m);
+  }
+  return v[0];
+}
+
 // (hand-off polls run back to back: a pause between them lost, DESIGN.md Appendix A "poll sleep")
 __device__ __forceinline__ bool timed_out(unsigned long long deadline) {
   return __builtin_amdgcn_s_memrealtime() > deadline;
@@ -184,6 +204,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   const float thr = A.threshold;
   const float inv_thr = 1.0f / thr;
   const bool keep = A.keep_outliers != 0;
+  const TotalLane tl = total_lane(A, lane);  // the finishing wave: lane e converts total e
 
   float chi_prev = FLT_MAX;  // the leader's loop state besides the pose (exec/icp_test.cpp:89)
   unsigned long long pose_sink = 0, pa = 0, pb = 0;  // the follower's pose polls
@@ -321,19 +342,21 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           }
         }
       }
+      // every gv[i]: a block's granule pair, or the zeros it started with where g + NG*i is past
+      // the problem's blocks (never loaded).  Adding those zeros is exact and the sum cannot be
+      // -0 (it starts at +0), so no guard per i: the same bits, i ascending
       double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
-      for (int i = 0; i < MAXG; ++i)
-        if (g + NG * i < nblk) {
-          acc0 += (double)__uint_as_float(gv[i][0]);
-          acc1 += (double)__uint_as_float(gv[i][2]);
-        }
+      for (int i = 0; i < MAXG; ++i) {
+        acc0 += (double)__uint_as_float(gv[i][0]);
+        acc1 += (double)__uint_as_float(gv[i][2]);
+      }
       // the wave's four groups (lanes c, 16+c, 32+c, 48+c) first: every lane ends with the same
       // (a0+a1)+(a2+a3) (IEEE addition commutes), so the order stays fixed
-      acc0 += __shfl_xor(acc0, 16);
-      acc1 += __shfl_xor(acc1, 16);
-      acc0 += __shfl_xor(acc0, 32);
-      acc1 += __shfl_xor(acc1, 32);
+      acc0 = wave_add_xor_f64<16>(acc0);
+      acc1 = wave_add_xor_f64<16>(acc1);
+      acc0 = wave_add_xor_f64<32>(acc0);
+      acc1 = wave_add_xor_f64<32>(acc1);
       if (lane < 16) {
         s_red[2 * c][wave] = acc0;
         s_red[2 * c + 1][wave] = acc1;
@@ -366,7 +389,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           double t = ws[0];
 #pragma unroll
           for (int w = 1; w < BS / 64; ++w) t += ws[w];
-          s_tot[lane] = total_word(A, lane, t);  // lane e converts total e
+          s_tot[lane] = total_word(tl, t);  // lane e converts total e
         }
         __builtin_amdgcn_wave_barrier();
         {
@@ -375,15 +398,19 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           PSTAMP(4);
           finish_round_pose(A, s_tot, (int)epoch, pr, pt, chi_prev, o);
           PSTAMP(5);
+          // (read here, after the solve: hoisted to the combine's loads it measured no faster,
+          // DESIGN.md Appendix A "s_tmo read early")
           if (s_tmo) o.done = 1;  // a sweep timed out
           // ---- publish the new pose (and the done flag): lane l < 16 owns word l ----
-          float w = 0.0f;
+          unsigned pw[PICP_POSE_GRAN];
 #pragma unroll
-          for (int i = 0; i < 9; ++i) w = (lane == i) ? pr[i] : w;
+          for (int i = 0; i < 9; ++i) pw[i] = __float_as_uint(pr[i]);
 #pragma unroll
-          for (int i = 0; i < 3; ++i) w = (lane == 9 + i) ? pt[i] : w;
-          w = (lane == 12) ? __int_as_float(o.done) : w;
-          w = (lane == 13) ? __uint_as_float(my_xcc) : w;
+          for (int i = 0; i < 3; ++i) pw[9 + i] = __float_as_uint(pt[i]);
+          pw[12] = (unsigned)o.done;
+          pw[13] = my_xcc;
+          pw[14] = pw[15] = 0u;
+          const float w = __uint_as_float(lane_word16(pw, lane));
           if (lane < PICP_POSE_GRAN) {
             const unsigned long long gw = granule(tbase + epoch, w);
             __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
