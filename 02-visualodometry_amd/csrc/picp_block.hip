@@ -14,10 +14,11 @@
 // Split (split = 2 or 4): when S x the problems still fit on the chip (C4: 128 frames, 256 CUs),
 // each problem runs on S blocks, each with 1/S of the correspondences, so no CU idles.  Per
 // round each block publishes its 32-term partial as 64 granules {round, hi|lo} (the double sum
-// as hi = (float)t, lo = (float)(t - hi)), polls its S - 1 partners', and all add the parts in
-// part order: every part runs the identical solve, so no broadcast is needed.  Partners are
-// blockIdx b, b + 8, b + 16, ... which round-robin placement puts on the same XCD (speed only:
-// correctness rests on the tags).  Granules are double-buffered by round parity; their tags
+// as hi = (float)t, lo = (float)(t - hi); lo = 0 under a non-finite hi), polls its S - 1
+// partners', and all add the parts in part order: every part runs the identical solve, so no
+// broadcast is needed.  Partners are blockIdx b, b + 8, b + 16, ... which round-robin placement
+// puts on the same XCD (speed only: correctness rests on the tags).
+// Granules are double-buffered by round parity; their tags
 // continue from per-slot tag bases the previous launch left, so the sync area is zeroed only once
 // per layout (and before the tags could wrap), not per launch.  Every wait has an s_memrealtime
 // deadline, refreshed each round (error word set, the problem stops, the host reports it and
@@ -408,7 +409,9 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
       for (int w = 1; w < BS / 64; ++w) t += (double)ws[w];
       if (split > 1) {
         // publish {round, hi}, {round, lo}; poll the partners'; add the parts in part order
-        const float hi = (float)t, lo = (float)(t - (double)hi);
+        // (an infinite total -- chi_out of an overflowing measurement -- has no low part: inf - inf
+        // would publish NaN and the partners would read inf + NaN)
+        const float hi = (float)t, lo = (fabsf(hi) <= FLT_MAX) ? (float)(t - (double)hi) : 0.0f;
         const size_t slot = (size_t)(round & 1) * gridDim.x;
         bgu64_t* mine = xgg + (slot + blockIdx.x) * PICP_XG;
         const unsigned tag = tbase + (unsigned)round;

@@ -221,6 +221,12 @@ __device__ __forceinline__ void accumulate_one(const Pose& T, const Cam& C, floa
 //   a00 = fx/z, a02 = cx/z - ph0/z^2, a11 = fy/z, a12 = cy/z - ph1/z^2
 //   J0 = [a00, 0, a02, a02 pc1, a00 pc2 - a02 pc0, -a00 pc1]
 //   J1 = [0, a11, a12, a12 pc1 - a11 pc2, -a12 pc0, a11 pc0]
+// For a used item whose Jacobian is not finite (a NaN point passes the gate as in the reference)
+// the reference's products with K's zeros are NaN, not 0.  Every entry of H and b but H(0,1) keeps
+// a term that carries the NaN; H(0,1) consists of dropped terms only.  The pair form adds them
+// back in the waves that take the division (pinhole2_h01_dropped), so picp_linearize returns the
+// reference's all-NaN H; the one-slot form leaves H(0,1) = 0 there (the solve of such an H gives a
+// NaN pose either way).
 // The structural zeros drop 12 of the 54 multiply-adds of H and b, and lambda = sqrt(thr/chi)
 // comes from v_rsq (it only weighs kept outliers, within the H/b tolerance): ~1/3 fewer VALU
 // instructions per correspondence than the general path.  KEEP (keep_outliers, compile time):
@@ -481,6 +487,36 @@ __device__ __forceinline__ bool pair_rcp_safe(const Pose& T, f2 x, f2 y, f2 z) {
   return rcp_safe(d.x) & rcp_safe(d.y);
 }
 
+// What the sparse pinhole form drops from H(0,1), for the waves that take the division (a lane
+// holds an extreme depth): w (J(0,0) J(0,1) + J(1,0) J(1,1)) of a used item with the reference's
+// J(0,1) = iz*0 + jp0*0 and J(1,0) = iz*0 + jp1*0 (src/picp_solver.cpp:47-52, the products with
+// K's zeros): +-0 while iz and jp are finite -- H(0,1) keeps its bits -- and NaN otherwise, so an
+// item that passes the gate with a NaN or infinite Jacobian (NaN passes as in the reference)
+// makes H(0,1) NaN as it makes every other entry.  The gate is restated here, inside the rare
+// branch, so that the common path keeps its instruction stream: this is a SECOND COPY of the
+// bounds test, chi, inlier / use flags and robust weight of accumulate_pinhole2 below and has to
+// change with them.
+template <bool KEEP>
+__device__ __forceinline__ f2 pinhole2_h01_dropped(const Cam& C, float thr, float inv_thr, f2 ph0, f2 ph1,
+                                                   f2 pc2, f2 iz, f2 u, f2 v, bool inA, bool inB) {
+#pragma clang fp contract(off)
+  const f2 ix = ph0 * iz, iy = ph1 * iz;
+  const bool validA = inA & !(pc2.x <= 0.0f) & !((ix.x < 0.0f) | (ix.x > C.maxx) | (iy.x < 0.0f) | (iy.x > C.maxy));
+  const bool validB = inB & !(pc2.y <= 0.0f) & !((ix.y < 0.0f) | (ix.y > C.maxx) | (iy.y < 0.0f) | (iy.y > C.maxy));
+  const f2 e0 = ix - u, e1 = iy - v;
+  const f2 chi = e0 * e0 + e1 * e1;
+  const bool inlA = validA & !(chi.x > thr), inlB = validB & !(chi.y > thr);
+  const bool useA = inlA | (validA & KEEP), useB = inlB | (validB & KEEP);
+  const f2 iz2 = iz * iz;
+  const f2 j01 = iz * 0.0f + -(ph0 * iz2) * 0.0f, j10 = iz * 0.0f + -(ph1 * iz2) * 0.0f;
+  f2 t = (iz * C.k00) * j01 + j10 * (iz * C.k11);
+  if constexpr (KEEP) {
+    const f2 q = chi * inv_thr;
+    t = (f2){(inlA ? 1.0f : __builtin_amdgcn_rsqf(q.x)) * t.x, (inlB ? 1.0f : __builtin_amdgcn_rsqf(q.y)) * t.y};
+  }
+  return (f2){useA ? t.x : 0.0f, useB ? t.y : 0.0f};
+}
+
 template <bool KEEP, int RCP = RCP_CHECK>
 __device__ __forceinline__ void accumulate_pinhole2(const Pose& T, const Cam& C, float thr,
                                                     float inv_thr, f2 x, f2 y, f2 z,
@@ -502,10 +538,12 @@ __device__ __forceinline__ void accumulate_pinhole2(const Pose& T, const Cam& C,
     } else {
       iz.x = 1.0f / pc2.x;
       iz.y = 1.0f / pc2.y;
+      a.h[1] += pinhole2_h01_dropped<KEEP>(C, thr, inv_thr, ph0, ph1, pc2, iz, u, v, inA, inB);
     }
     const f2 ix = ph0 * iz;
     const f2 iy = ph1 * iz;
     // bitwise, not short-circuit: the same predicate without per-item exec-mask branches
+    // (this gate, down to the weight, has a second copy in pinhole2_h01_dropped: keep them in step)
     validA = inA & !(pc2.x <= 0.0f) &
              !((ix.x < 0.0f) | (ix.x > C.maxx) | (iy.x < 0.0f) | (iy.x > C.maxy));
     validB = inB & !(pc2.y <= 0.0f) &
@@ -524,7 +562,7 @@ __device__ __forceinline__ void accumulate_pinhole2(const Pose& T, const Cam& C,
              useB ? (inlB ? 1.0f : __builtin_amdgcn_rsqf(q.y)) : 0.0f};
   }
   acc2_stats(chi, inlA, inlB, validA, validB, a, n);
-  // a skipped item gets weight 0 and finite inputs, so it can never inject inf/NaN.  (Skipping
+  // a skipped item gets weight 0 and zeroed inputs, so it can never inject inf/NaN.  (Skipping
   // these selects for waves of projectable items, as accumulate_pinhole does, measured 1-4 %
   // slower here: the branches split the unrolled pairs' straight-line schedule.)
 #define PICP_Z2(val) val = (f2){useA ? val.x : 0.0f, useB ? val.y : 0.0f}
