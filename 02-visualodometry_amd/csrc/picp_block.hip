@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "picp_vo_device.h"
+#include "picp_launch.h"
 
 using namespace picp;
 

@@ -18,6 +18,7 @@
 //   vo_track_kernel      : the VO sequence's per-map-point counters: one block per segment over
 //                          the step's frame->map matches (shaped like vo_gather_kernel).
 #include "picp_device.h"
+#include "picp_launch.h"
 
 using namespace picp;
 

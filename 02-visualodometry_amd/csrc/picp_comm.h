@@ -1,5 +1,5 @@
 // picp_comm.h -- runtime-internal view of the RCCL communicator (picp_comm.cpp) for the batch
-// all-gather in picp_runtime.cpp.  Not installed.
+// all-gather in picp_batch.cpp.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "picp_internal.h"
+#include "picp_launch.h"
 
 #pragma clang fp contract(off)
 

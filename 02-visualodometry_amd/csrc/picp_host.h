@@ -2,42 +2,41 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "picp_c.h"
+#include <stdint.h>
 
-// the descriptor matcher's launchers (picp_match.hip)
-extern "C" hipError_t picp_launch_match_prep(hipStream_t stream, const float* desc, int64_t n, int dim,
-                                             _Float16* h, float* n1, float* n2);
-extern "C" hipError_t picp_launch_match_mfma(hipStream_t stream, int n_problems, int64_t max_nq,
-                                             const float* q_desc, const float* r_desc,
-                                             const _Float16* q_h, const float* q_n1,
-                                             const _Float16* r_h, const float* r_n1, const float* r_n2,
-                                             const struct MatchProblem* probs, int dim, float dist_thr,
-                                             float ratio_thr, int32_t* best_idx, float* best_dist,
-                                             float* second_dist, int32_t* accepted, int form, int ksplit,
-                                             float4* part, int64_t part_cap);
-extern "C" hipError_t picp_launch_match_mfma_parts(hipStream_t stream, int n_problems, int64_t max_nq,
-                                                   const float* q_desc, const float* r_desc, const _Float16* q_h,
-                                                   const float* q_n1, const _Float16* r_h, const float* r_n1,
-                                                   const float* r_n2, const struct MatchProblem* probs, int dim,
-                                                   float dist_thr, float ratio_thr, int form, int ksplit, int slot0,
-                                                   float4* part, int64_t part_cap);
-extern "C" hipError_t picp_launch_match_merge(hipStream_t stream, const struct MatchProblem* probs, int n_problems,
-                                              int64_t max_nq, int ksplit, int extra, const float4* part,
-                                              int64_t part_cap, float dist_thr, float ratio_thr,
-                                              int32_t* best_idx, float* best_dist, float* second_dist,
-                                              int32_t* accepted);
-// picp_match_ksplit reads PICP_MATCH_KSPLIT each call; picp_match_ksplit_forced takes the forced
-// count (0: none) from the caller, so a handle can read the variable once and size its scratch and
-// its launches from the same value
-extern "C" int picp_match_ksplit(int n_problems, int64_t max_nq, int64_t max_nr, int form);
-extern "C" int picp_match_ksplit_forced(int n_problems, int64_t max_nq, int64_t max_nr, int form, int force);
-extern "C" int picp_match_ksplit_env(void);
-// float4 of scratch a split launch needs (the ranges' partials)
-extern "C" int64_t picp_match_split_scratch(int ksplit, int n_problems, int64_t max_nq);
-extern "C" int picp_match_prep_kch(int dim);
+#include "picp_c.h"
+#include "picp_internal.h"
+
+#pragma GCC visibility push(hidden)
 
 // records the thread's last error message (picp_last_error) and returns `code`
-__attribute__((visibility("hidden"), format(printf, 2, 3))) int picp_set_err(int code, const char* fmt, ...);
+__attribute__((format(printf, 2, 3))) int picp_set_err(int code, const char* fmt, ...);
+
+// pose helpers (column-major 4x4 <-> state R(col-major 3x3), t), picp_runtime.cpp
+void pose_to_state(const float T[16], PicpState& s);
+void state_to_pose(const PicpState& s, float T[16]);
+void state_to_stats(const PicpState& s, picp_stats& st);
+
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// Device buffer *ptr of *cap elements of `elem` bytes, discarded and allocated anew (at least 256
+// elements) when `need` elements do not fit; the contents are not kept.  picp_runtime.cpp
+int grow(void** ptr, int64_t* cap, int64_t need, size_t elem);
+
+// hipEvents destroyed on every return path
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipError_t create() {
+    hipError_t e = hipEventCreate(&a);
+    return e == hipSuccess ? hipEventCreate(&b) : e;
+  }
+  ~EventPair() {
+    if (a) hipEventDestroy(a);
+    if (b) hipEventDestroy(b);
+  }
+};
+
+#pragma GCC visibility pop
 
 #define HIP_TRY(expr)                                                                       \
   do {                                                                                      \

@@ -13,11 +13,8 @@
 #pragma once
 #include <stdint.h>
 
-#define PICP_BLOCK 256            // threads per linearize block (4 waves of 64)
-#define PICP_NPART 32             // floats per block partial (31 used)
-// persistent mode: pose granule sets per problem -- solver g (g < 8) publishes an L2-kept copy
-// (set 2g) and an agent-scope copy (set 2g + 1), 16 granules (one 128-B line) each
-#define PICP_POSE_SETS 16
+#include "picp_problem.h"  // PICP_BLOCK, PICP_NPART, PICP_POSE_SETS, PicpProblem
+
 // partial slot layout
 #define PICP_P_H 0                // 21 upper-triangle entries of H (row-major upper)
 #define PICP_P_B 21               // 6 entries of b
@@ -25,15 +22,6 @@
 #define PICP_P_CHI_OUT 28
 #define PICP_P_N_IN 29
 #define PICP_P_N_PROJ 30
-
-// Ragged batches only: per-problem partition (uniform batches compute it from blockIdx).
-struct PicpProblem {
-  int64_t offset;      // first item in the SoA planes (multiple of 4)
-  int32_t n;           // number of correspondences
-  int32_t blk0;        // first linearize block (index into partials) of this problem
-  int32_t nblk;        // number of linearize blocks (>= 1)
-  int32_t pad;
-};
 
 // Batch-wide launch arguments, passed BY VALUE (kernel-argument SGPRs: no memory hop).
 struct PicpArgs {
@@ -97,7 +85,6 @@ struct RefinePose {
 
 static_assert(sizeof(RefinePose) == 48, "RefinePose must be 48 B");
 static_assert(sizeof(PicpState) == 128, "PicpState must be 128 B");
-static_assert(sizeof(PicpProblem) % 8 == 0, "PicpProblem alignment");
 
 // ---------------------------------------------------------------------------------------
 // descriptor matching (picp_match.hip): query rows [q_off, q_off + nq) of the query

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "picp_internal.h"
+#include "picp_launch.h"
 
 // Diagnostic build only (-DPICP_STAMPS, lib/libpicp_amd_stamps.so): thread 0 of each block
 // records s_memrealtime (100 MHz) at phase boundaries of launches j = 10 and 11 into a buffer
@@ -350,7 +351,7 @@ extern "C" __global__ void picp_triangulate_kernel(const float* __restrict__ P1,
 }
 
 // ------------------------------- host launch wrappers -------------------------------
-// (called by picp_runtime.cpp; every shape/grid assumption is checked there first)
+// (declared in picp_launch.h; every shape/grid assumption is checked by the calling runtime first)
 extern "C" hipError_t picp_launch_round(hipStream_t stream, int grid, int vec, const float* X,
                                         const float* Y, const float* Z, const float* U,
                                         const float* V, const PicpArgs* args,
@@ -417,4 +418,10 @@ extern "C" __global__ void picp_rcp_check_kernel(int e_lo, int e_hi, unsigned lo
   const unsigned bits = ((rem >> 23) << 31) | ((unsigned)(e + 127) << 23) | (rem & 0x7fffffu);
   const float x = __uint_as_float(bits);
   if (__float_as_uint(rcp_rn(x)) != __float_as_uint(1.0f / x)) atomicAdd(bad, 1ull);
+}
+
+extern "C" hipError_t picp_launch_rcp_check(hipStream_t stream, int e_lo, int e_hi, unsigned long long* bad) {
+  const int64_t n = (int64_t)(e_hi - e_lo) << 24;
+  hipLaunchKernelGGL(picp_rcp_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, e_lo, e_hi, bad);
+  return hipGetLastError();
 }

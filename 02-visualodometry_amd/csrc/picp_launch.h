@@ -1,0 +1,107 @@
+// picp_launch.h -- every symbol a host translation unit (.cpp) calls and a device translation
+// unit (.hip) defines: the kernel launchers and the queries of the kernels' compile-time shapes.
+// Included by the defining .hip and by every caller, so a signature that changes on one side only
+// is a compile error.  Not installed; not part of the public C-ABI (include/picp_c.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "picp_c.h"
+#include "picp_internal.h"
+
+extern "C" {
+
+// ---- picp_kernels.hip
+hipError_t picp_launch_round(hipStream_t stream, int grid, int vec, const float* X, const float* Y,
+                             const float* Z, const float* U, const float* V, const PicpArgs* args,
+                             const PicpProblem* probs, const int4* blkinfo, const PicpState* st_in,
+                             PicpState* st_out, unsigned long long* part, unsigned int* tickets, int j);
+hipError_t picp_launch_gather(hipStream_t stream, const float* world, const float* image, const int2* pairs,
+                              int64_t m, float* X, float* Y, float* Z, float* U, float* V, int64_t off);
+hipError_t picp_launch_triangulate(hipStream_t stream, const float* P1, const float* P2, const float2* uv1,
+                                   const float2* uv2, int64_t q, float* xyz);
+// counts into *bad the floats of binades [e_lo, e_hi), both signs, whose rcp_rn differs from 1.0f / x
+hipError_t picp_launch_rcp_check(hipStream_t stream, int e_lo, int e_hi, unsigned long long* bad);
+
+// ---- picp_persistent.hip
+hipError_t picp_launch_persistent(hipStream_t stream, int grid, int npt, const float* X, const float* Y,
+                                  const float* Z, const float* U, const float* V, const PicpArgs* args,
+                                  const PicpState* st_in, PicpState* st_out, unsigned long long* gpart,
+                                  unsigned long long* gpose, unsigned int* err, unsigned int* tagbase,
+                                  unsigned long long timeout_ticks);
+int picp_persistent_block(void);
+hipError_t picp_persistent_occupancy(int npt, const float K[9], int* blocks_per_cu);
+
+// ---- picp_block.hip
+hipError_t picp_launch_block(hipStream_t stream, int n_problems, int npt, const float* X, const float* Y,
+                             const float* Z, const float* U, const float* V, const PicpArgs* args,
+                             const PicpProblem* probs, const PicpState* st_in, PicpState* st_out, int max_n,
+                             int split, unsigned long long* xg, unsigned int* err, unsigned int* tagbase,
+                             unsigned long long timeout_ticks);
+int picp_block_max_items(void);
+int picp_block_threads(int split);
+int picp_block_npt_cap(int split);
+hipError_t picp_block_occupancy(int npt, int split, int max_n, const float K[9], int* blocks_per_cu);
+int picp_vo_block_fusable(int npt, int64_t max_obs);
+hipError_t picp_launch_vo_block(hipStream_t stream, const VoArgs* a, int t, int npt, const PicpArgs* args,
+                                int64_t max_obs);
+
+// ---- picp_vo.hip
+hipError_t picp_launch_vo_gather(hipStream_t stream, const VoArgs* a, int t);
+hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a, int t);
+
+// ---- picp_classify.hip
+int picp_classify_tile(void);
+hipError_t picp_launch_classify(hipStream_t stream, int nb, int np, const float* X, const float* Y,
+                                const float* Z, const float* U, const float* V, const ClsArgs* a,
+                                const int4* blk, const int2* pblk, const int64_t* plane_off,
+                                const int64_t* pack_off, const PicpState* st, uint8_t* state, float* chi2,
+                                float* uv, int* cnt, long long* base, long long* counts, long long* inl_off,
+                                int32_t* idx);
+hipError_t picp_launch_vo_track(hipStream_t stream, const VoArgs* a, int t, const ClsArgs* c, int* n_matched,
+                                int* n_inlier);
+
+// ---- picp_refine.hip
+hipError_t picp_launch_refine(hipStream_t stream, const RefineArgs* a, const RefinePose* poses,
+                              const int64_t* track_off, const int32_t* obs_pose, const float2* obs_uv,
+                              float* xyz, picp_stats* stats);
+
+// ---- picp_essential.hip
+hipError_t picp_launch_essential(hipStream_t stream, const EssArgs* args, const int64_t* offs, const float* p1,
+                                 const float* p2, int32_t* idx, double* Es, int32_t* ns, int32_t* cnt,
+                                 float* T_out, int32_t* inliers, int32_t* good, uint8_t* mask);
+
+// ---- picp_match.hip
+hipError_t picp_launch_match(hipStream_t stream, int n_problems, int64_t max_nq, const float* q_desc,
+                             const float* r_desc, const MatchProblem* probs, int dim, float dist_thr,
+                             float ratio_thr, int32_t* best_idx, float* best_dist, float* second_dist,
+                             int32_t* accepted);
+hipError_t picp_launch_match_prep(hipStream_t stream, const float* desc, int64_t n, int dim, _Float16* h,
+                                  float* n1, float* n2);
+hipError_t picp_launch_match_mfma(hipStream_t stream, int n_problems, int64_t max_nq, const float* q_desc,
+                                  const float* r_desc, const _Float16* q_h, const float* q_n1,
+                                  const _Float16* r_h, const float* r_n1, const float* r_n2,
+                                  const MatchProblem* probs, int dim, float dist_thr, float ratio_thr,
+                                  int32_t* best_idx, float* best_dist, float* second_dist, int32_t* accepted,
+                                  int form, int ksplit, float4* part, int64_t part_cap);
+hipError_t picp_launch_match_mfma_parts(hipStream_t stream, int n_problems, int64_t max_nq, const float* q_desc,
+                                        const float* r_desc, const _Float16* q_h, const float* q_n1,
+                                        const _Float16* r_h, const float* r_n1, const float* r_n2,
+                                        const MatchProblem* probs, int dim, float dist_thr, float ratio_thr,
+                                        int form, int ksplit, int slot0, float4* part, int64_t part_cap);
+hipError_t picp_launch_match_merge(hipStream_t stream, const MatchProblem* probs, int n_problems, int64_t max_nq,
+                                   int ksplit, int extra, const float4* part, int64_t part_cap, float dist_thr,
+                                   float ratio_thr, int32_t* best_idx, float* best_dist, float* second_dist,
+                                   int32_t* accepted);
+// picp_match_ksplit reads PICP_MATCH_KSPLIT each call; picp_match_ksplit_forced takes the forced
+// count (0: none) from the caller, so a handle can read the variable once and size its scratch and
+// its launches from the same value
+int picp_match_ksplit(int n_problems, int64_t max_nq, int64_t max_nr, int form);
+int picp_match_ksplit_forced(int n_problems, int64_t max_nq, int64_t max_nr, int form, int force);
+int picp_match_ksplit_env(void);
+// float4 of scratch a split launch needs (the ranges' partials)
+int64_t picp_match_split_scratch(int ksplit, int n_problems, int64_t max_nq);
+int picp_match_prep_kch(int dim);
+
+}  // extern "C"

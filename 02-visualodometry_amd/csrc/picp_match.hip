@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "picp_internal.h"
+#include "picp_launch.h"
 
 #define PICP_MATCH_BLOCK 256
 #define PICP_MATCH_QPL 2  // queries per lane: (query A, query B) packed in one float2

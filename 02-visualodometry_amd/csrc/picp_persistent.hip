@@ -21,6 +21,7 @@
 // tags are offset by a per-problem round counter kept on the device (tagbase), so granules left
 // by earlier launches never match and no memset runs between launches.
 #include "picp_device.h"
+#include "picp_launch.h"
 
 using namespace picp;
 

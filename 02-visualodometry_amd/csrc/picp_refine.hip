@@ -25,6 +25,7 @@
 #include "picp_device.h"
 
 #include "picp_c.h"
+#include "picp_launch.h"
 
 using namespace picp;
 

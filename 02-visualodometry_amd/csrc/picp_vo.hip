@@ -24,6 +24,7 @@
 // Ordered compaction = wave ballot + popcount prefix + an LDS scan over the block's waves, so
 // map order and correspondence order equal the reference's sequential push_back order.
 #include "picp_vo_device.h"
+#include "picp_launch.h"
 
 using namespace picp;
 

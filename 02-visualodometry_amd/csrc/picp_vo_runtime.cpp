@@ -21,21 +21,7 @@
 #include "picp_c.h"
 #include "picp_host.h"
 #include "picp_internal.h"
-
-extern "C" hipError_t picp_launch_block(hipStream_t stream, int n_problems, int npt, const float* X,
-                                        const float* Y, const float* Z, const float* U,
-                                        const float* V, const PicpArgs* args,
-                                        const PicpProblem* probs, const PicpState* st_in,
-                                        PicpState* st_out, int max_n, int split,
-                                        unsigned long long* xg, unsigned int* err,
-                                        unsigned int* tagbase, unsigned long long timeout_ticks);
-extern "C" hipError_t picp_launch_vo_gather(hipStream_t stream, const VoArgs* a, int t);
-extern "C" int picp_vo_block_fusable(int npt, int64_t max_obs);
-extern "C" hipError_t picp_launch_vo_block(hipStream_t stream, const VoArgs* a, int t, int npt,
-                                           const PicpArgs* args, int64_t max_obs);
-extern "C" hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a, int t);
-extern "C" hipError_t picp_launch_vo_track(hipStream_t stream, const VoArgs* a, int t, const ClsArgs* c,
-                                           int* n_matched, int* n_inlier);
+#include "picp_launch.h"
 
 static_assert(sizeof(picp_vo_step) == sizeof(VoStep), "picp_vo_step must mirror VoStep");
 

@@ -35,7 +35,7 @@ def _case(name, mode, sizes, rounds, seed, keep=0, of=0.1, conv_eps=-1.0, dampin
 def _cases():
     out = []
     # persistent mode, one frame; 50 rounds only where the oracle is cheap.  A frame of more than
-    # 512 x CUs correspondences is partitioned by the CU count (picp_runtime.cpp)
+    # 512 x CUs correspondences is partitioned by the CU count (picp_layout.cpp)
     for tag, n, rounds in (("solo", 300, 50), ("solvers8", 4096, 50), ("follower1", 9 * 512 - 5, 5),
                            ("blocks33", 33 * 512, 5), ("blocks256", 131072, 5), ("npt2", 140000, 5)):
         for keep in (0, 1):
