@@ -38,6 +38,10 @@ typedef __attribute__((address_space(1))) unsigned int gu32_t;
 // range: no memory access, a zero), so both passes' loads are unconditional and the waits count
 // exactly one pass.  C3 150.5k -> 156.5k it/s (8 x 64 clocks; 16: 155k); with one item per lane
 // (C2) -2 %, so it starts at PICP_SWEEP_MIN_NPT items (profiles/r05/sweep_stagger/).
+// As compiled, take(gb) is scheduled above issue(ga), so after the first iteration the two
+// passes are issued back to back and both are waited for; with the order forced (a scheduling
+// barrier after issue(ga)) C3 lost 4.5 %, with one pass only 2.4 % (DESIGN.md Appendix A, round
+// 11), so the source and that schedule stay.
 #define PICP_SWEEP_STAGGER 8
 #define PICP_SWEEP_MIN_NPT 2  // the staggered sweep from this many items per lane on
 #define PICP_POSE_GRAN 16   // pose granules per set: R(9) t(3) done(1) solver XCC id(1) pad(2)
@@ -61,11 +65,18 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // Diagnostic build only (-DPICP_STAMPS): s_memrealtime per phase of rounds (epochs) 11 and 12.
 #ifdef PICP_STAMPS
 __device__ unsigned long long picp_pstamps[2][256][8];
-#define PSTAMP(k)                                                                              \
+#define PSTAMP_T(k, t)                                                                         \
   do {                                                                                         \
-    if (threadIdx.x == 0 && (epoch == 11 || epoch == 12) && blockIdx.x < 256)                  \
+    if (threadIdx.x == (t) && (epoch == 11 || epoch == 12) && blockIdx.x < 256)                \
       picp_pstamps[epoch - 11][blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();               \
   } while (0)
+#define PSTAMP(k) PSTAMP_T(k, 0)
+// What a round waits for besides its hand-offs (slots 6 and 7).  A follower: thread 64 (wave 1,
+// which never polls) stamps the round start (6) and the pose barrier (7) beside wave 0's stamps
+// 0 and 2, so the stretch barrier -> next round start can be compared between the polling wave
+// and one that has nothing in flight.  A solver: thread 0 at the sweep's exit (6) and after the
+// double sums (7), the stretch that holds the wait for a sweep pass still in flight.
+#define PSTAMP_W1(k) PSTAMP_T(k, 64)
 extern "C" hipError_t picp_debug_pstamps(unsigned long long* out, size_t n_words);
 // the leader's sweep, thread 0 (wave 0): each pass's issue and return times, rounds 11 and 12
 __device__ unsigned long long picp_sweepstamps[2][64];
@@ -81,6 +92,9 @@ extern "C" hipError_t picp_debug_sweepstamps(unsigned long long* out, size_t n_w
   } while (0)
 #define PSTAMP(k) \
   do {            \
+  } while (0)
+#define PSTAMP_W1(k) \
+  do {               \
   } while (0)
 #endif
 
@@ -129,10 +143,15 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   __shared__ double s_red[PICP_NPART][BS / 64];  // term-major: one row per combining lane
   __shared__ float s_tot[PICP_NPART];
   __shared__ float s_wave[BS / 64][PICP_NPART];
-  __shared__ float s_pose[12];
-  __shared__ int s_done;
+  // The round's control words, one 16-word row so that a follower's polling wave stores what it
+  // received with one LDS store per lane (lane l < 14 writes word l): the pose, the done flag and
+  // whether this follower runs on its solver's XCD (then it polls the L2 copy of the pose).
+  // (As three objects the stores were six exec-mask branches in front of the pose barrier.)
+  __shared__ unsigned s_ctl[16];
+  float* const s_pose = (float*)s_ctl;  // words 0-11: R (9), t (3)
+  int& s_done = *(int*)&s_ctl[12];
+  int& s_l2 = *(int*)&s_ctl[13];
   __shared__ int s_tmo;  // a wait of this block timed out (the error word is for the host)
-  __shared__ int s_l2;   // a follower on its solver's XCD: poll the L2 copy of the pose
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nblk = A.nblk_u;
@@ -207,6 +226,12 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   const bool keep = A.keep_outliers != 0;
   const TotalLane tl = total_lane(A, lane);  // the finishing wave: lane e converts total e
 
+  // The slice has landed before the first round: the round loop's waits then count nothing that
+  // was issued before it, so a follower's poll left in flight (below) is never waited for by the
+  // linearize's first use of an item.
+#pragma unroll
+  for (int k = 0; k < NPT; ++k) asm volatile("" ::"v"(xs[k]), "v"(ys[k]), "v"(zs[k]), "v"(us[k]), "v"(vs[k]));
+
   float chi_prev = FLT_MAX;  // the leader's loop state besides the pose (exec/icp_test.cpp:89)
   unsigned long long pose_sink = 0, pa = 0, pb = 0;  // the follower's pose polls
   for (unsigned epoch = 1; !s_done; ++epoch) {
@@ -215,6 +240,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     const unsigned long long deadline = __builtin_amdgcn_s_memrealtime() + timeout_ticks;
     // ---- 1. linearize the slice at the current pose, publish the block partial ----
     PSTAMP(0);
+    if (!solver) PSTAMP_W1(6);
     Pose T;
     T.r00 = s_pose[0]; T.r10 = s_pose[1]; T.r20 = s_pose[2];
     T.r01 = s_pose[3]; T.r11 = s_pose[4]; T.r21 = s_pose[5];
@@ -346,6 +372,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       // every gv[i]: a block's granule pair, or the zeros it started with where g + NG*i is past
       // the problem's blocks (never loaded).  Adding those zeros is exact and the sum cannot be
       // -0 (it starts at +0), so no guard per i: the same bits, i ascending
+      PSTAMP(6);
       double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
       for (int i = 0; i < MAXG; ++i) {
@@ -354,6 +381,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       }
       // the wave's four groups (lanes c, 16+c, 32+c, 48+c) first: every lane ends with the same
       // (a0+a1)+(a2+a3) (IEEE addition commutes), so the order stays fixed
+      PSTAMP(7);
       acc0 = wave_add_xor_f64<16>(acc0);
       acc1 = wave_add_xor_f64<16>(acc1);
       acc0 = wave_add_xor_f64<32>(acc0);
@@ -434,6 +462,10 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       }
       __syncthreads();
       PSTAMP(3);
+      // A solver has no poll in flight.  Defined here, the follower's poll state is dead on this
+      // path and does not merge with it at the bottom of the round: merged, the compiler copied
+      // the in-flight poll's registers on the follower's back edge and waited for the poll first.
+      pa = pb = pose_sink = 0;
     } else {
       // ---- 3. wait for the leader's pose of this round (one wave, 16 lanes) ----
       if (wave == 0) {
@@ -444,13 +476,18 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
         // in turn, measured no gain in round 2: they stay together).  Every lane loads (lanes >= 16
         // repeat granule 15), so the waits count exactly one poll; the poll still in flight at the
         // exit keeps its registers until the next round's wait consumes them (pose_sink), so
-        // nothing waits on it.
+        // nothing waits on it: pa, pb and pose_sink stay in the same registers round the loop
+        // (the solver path redefines them, above), the slice loads are retired before the loop,
+        // and last round's pair is folded into pose_sink before this round's first poll is issued
+        // (the empty asm pins the fold there: sunk below the spin, it would wait for the new poll).
+        // profiles/r11/waits/ has the back edge as compiled.
         const int gl = lane < PICP_POSE_GRAN ? lane : PICP_POSE_GRAN - 1;
         // sc1 loads either way: past the L1, served by the L2 (the L2 copy's line stays there)
         const gu64_t* src = s_l2 ? pose_l2 : pose_gl;
         auto poll = [&]() -> unsigned long long { return __hip_atomic_load(src + gl, RLX_AGENT); };
         auto good = [&](unsigned long long v) { return __all((unsigned)(v >> 32) == tbase + epoch); };
         pose_sink ^= pa ^ pb;  // last round's polls: long complete
+        asm volatile("" : "+v"(pose_sink));
         bool tmo = false;
         pa = poll();
         __builtin_amdgcn_s_sleep(PICP_POSE_STAGGER);
@@ -466,13 +503,14 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           gp = lane == 12 ? 1u : 0u;  // force done
           if (lane < 12) gp = __float_as_uint(s_pose[lane]);
         }
-        if (lane < 12) s_pose[lane] = __uint_as_float((unsigned)gp);
-        if (lane == 12) s_done = (int)(unsigned)gp;
-        // the solver's XCC id: from the next round on, poll the L2 copy when it is this XCD's
-        if (lane == 13) s_l2 = ((unsigned)gp == my_xcc) ? 1 : 0;
+        // lane l stores control word l: the pose (0-11), the done flag (12), and for the solver's
+        // XCC id (13) whether it is this XCD's: from the next round on, poll the L2 copy then
+        const unsigned cw = lane == 13 ? (((unsigned)gp == my_xcc) ? 1u : 0u) : (unsigned)gp;
+        if (lane < 14) s_ctl[lane] = cw;
       }
       __syncthreads();
       PSTAMP(2);
+      PSTAMP_W1(7);
     }
   }
   // an opaque never-true test keeps the follower's last in-flight poll alive to here

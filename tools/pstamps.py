@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Phase breakdown of the persistent kernel (diagnostic stamp build), rounds 11 and 12.
 Stamps: 0 round start, 1 partial published, 2 leader: sweep done / others: pose received,
-3 leader: solve done; and the leader's sweep passes (issue, return) of thread 0."""
+3 leader: solve done; the leader's sweep passes (issue, return) of thread 0; and what a round waits
+for besides its hand-offs (6, 7): in a follower, wave 1's round start and pose barrier beside the
+polling wave's (0, 2); in a solver, the sweep's exit and the end of the double sums."""
 import argparse
 import ctypes
 import os
@@ -52,6 +54,20 @@ def main():
         others = rel[ns:] if nb > ns else rel[1:]
         for k, nm in enumerate(["start", "published", "pose_received"]):
             print("  followers %-11s median %6d  min %6d  max %6d" % (nm, np.median(others[:, k]), others[:, k].min(), others[:, k].max()))
+        # what the round waits for besides its hand-offs (stamps 6 and 7)
+        print("  solver sweep exit -> double sums done: leader %d, solvers median %d (max %d)" % (
+            rel[0, 7] - rel[0, 6], np.median(rel[:ns, 7] - rel[:ns, 6]), (rel[:ns, 7] - rel[:ns, 6]).max()))
+        if r == 1 and nb > ns:
+            # a follower's pose barrier of round 11 -> its start of round 12: the polling wave
+            # (thread 0: stamps 2, 0) beside wave 1, which has nothing in flight (stamps 7, 6)
+            w0 = (buf[1, ns:nb, 0].astype(np.int64) - buf[0, ns:nb, 2].astype(np.int64)) * 10
+            w1 = (buf[1, ns:nb, 6].astype(np.int64) - buf[0, ns:nb, 7].astype(np.int64)) * 10
+            print("  followers pose barrier r11 -> start r12: polling wave median %d (min %d max %d), wave 1 median %d (min %d max %d)" % (
+                np.median(w0), w0.min(), w0.max(), np.median(w1), w1.min(), w1.max()))
+            # and on to the block's publish of round 12 (every wave's row is needed)
+            pub = (buf[1, ns:nb, 1].astype(np.int64) - buf[0, ns:nb, 2].astype(np.int64)) * 10
+            print("  followers pose barrier r11 -> published r12: median %d (min %d max %d)" % (
+                np.median(pub), pub.min(), pub.max()))
         last_pub = int(rel[:, 1].max())
         # the leader's sweep passes (thread 0): issue -> loads returned, ns from the round start
         p = sw[r].astype(np.int64)
