@@ -272,6 +272,13 @@ def projection_matrix(K, T_cw):
     return P.reshape(3, 4)
 
 
+def iso_inverse(T):
+    """Eigen::Isometry3f::inverse() in float32 (or_iso_inverse), 4x4 -> 4x4."""
+    out = np.zeros(16, np.float32)
+    lib().or_iso_inverse(_pose16(T), out)
+    return _pose44(out)
+
+
 def triangulate(P1, P2, uv1, uv2):
     uv1 = _f32(uv1).reshape(-1, 2)
     uv2 = _f32(uv2).reshape(-1, 2)

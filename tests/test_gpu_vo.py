@@ -27,6 +27,10 @@ What is compared, and how strictly:
   * the free-running sequence is chaotic (a 1e-7 difference in one step grows through the
     triangulated map; the oracle's own float32-vs-float64 accumulation modes drift apart by
     2.4e-3 over data/), so whole-trajectory agreement is a loose band only (2e-2).
+
+Every test here stays between 200 and 2,300 observations per frame with correspondences in every
+step; tests/test_gpu_vo_shapes.py runs the same step checks at the frame sizes where the driver
+changes its code path (up to 12,000 observations) and on empty and near-empty steps.
 """
 import numpy as np
 import pytest
@@ -57,19 +61,29 @@ def _se3(a, b):
     return se3_log_norm(rigid_inverse(np.asarray(a, np.float64)), rigid_inverse(np.asarray(b, np.float64)))
 
 
-def _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, map_xyz, map_desc):
-    """Re-run every step of one GPU segment on the oracle from the GPU's own inputs."""
+def _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, map_xyz, map_desc, stats=None):
+    """Re-run every step of one GPU segment on the oracle from the GPU's own inputs.  A step may
+    have no correspondence and may append nothing.  stats: optional dict that receives the
+    oracle solve's n_in and rounds per step and the worst triangulation residual ratio."""
     steps = len(poses) - 1
     m = int(rec["n_new"][0])
     worst_pose, tri_err, tri_ref = 0.0, [], []
+    if stats is not None:
+        stats.update({"n_in": [], "rounds": [], "res": stats.get("res", 0.0)})
     for t in range(steps):
         cf, nf = f0 + t, f0 + t + 1
         dn = desc[off[nf]:off[nf + 1]]
         wm = oracle.match_points(dn, map_desc[:m])
         assert wm["accepted"].sum() == rec["n_corr"][t + 1]
         pairs = np.stack([np.nonzero(wm["accepted"])[0], wm["best_idx"][wm["accepted"]]], 1).astype(np.int32)
-        T0 = np.linalg.inv(poses[t].astype(np.float64)).astype(np.float32)
-        T, _ = oracle.solve(T0, K, 480, 640, map_xyz[:m], uv[off[nf]:off[nf + 1]], pairs, THR)
+        if stats is None:
+            T0 = np.linalg.inv(poses[t].astype(np.float64)).astype(np.float32)
+        else:  # the step's own input: previous_pose.inverse() in float32, the bits the device starts from
+            T0 = oracle.iso_inverse(poses[t])
+        T, st = oracle.solve(T0, K, 480, 640, map_xyz[:m], uv[off[nf]:off[nf + 1]], pairs, THR)
+        if stats is not None:
+            stats["n_in"].append(st["n_in"])
+            stats["rounds"].append(st["rounds"])
         worst_pose = max(worst_pose, _se3(np.linalg.inv(T.astype(np.float64)), poses[t + 1]))
         pm = oracle.match_points(desc[off[cf]:off[cf + 1]], dn)
         sel = pm["accepted"].copy()
@@ -82,8 +96,10 @@ def _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, map_xyz, map_desc)
             P1 = oracle.projection_matrix(K, poses[t])
             P2 = oracle.projection_matrix(K, poses[t + 1])
             X = oracle.triangulate(P1, P2, uv[off[cf]:off[cf + 1]][ia], uv[off[nf]:off[nf + 1]][ib])
-            _assert_tri_residual(P1, P2, uv[off[cf]:off[cf + 1]][ia], uv[off[nf]:off[nf + 1]][ib],
-                                 map_xyz[m:m + len(ia)], "segment at frame %d, step %d" % (f0, t))
+            res = _assert_tri_residual(P1, P2, uv[off[cf]:off[cf + 1]][ia], uv[off[nf]:off[nf + 1]][ib],
+                                       map_xyz[m:m + len(ia)], "segment at frame %d, step %d" % (f0, t))
+            if stats is not None:
+                stats["res"] = max(stats["res"], res)
             tri_err.append(np.abs(map_xyz[m:m + len(ia)] - X).max(1))
             tri_ref.append(1.0 + np.abs(X).max(1))
         m += len(ia)
@@ -92,7 +108,7 @@ def _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, map_xyz, map_desc)
     return worst_pose, rel
 
 
-def _check_segment(oracle, K, off, uv, desc, f0, T0, T1, poses, rec, mx, md):
+def _check_segment(oracle, K, off, uv, desc, f0, T0, T1, poses, rec, mx, md, stats=None):
     # bootstrap: exactly the oracle's bootstrap map
     pm = oracle.match_points(desc[off[f0]:off[f0 + 1]], desc[off[f0 + 1]:off[f0 + 2]])
     ia = np.nonzero(pm["accepted"])[0]
@@ -100,11 +116,15 @@ def _check_segment(oracle, K, off, uv, desc, f0, T0, T1, poses, rec, mx, md):
     X = oracle.triangulate(oracle.projection_matrix(K, T0), oracle.projection_matrix(K, T1),
                            uv[off[f0]:off[f0 + 1]][ia], uv[off[f0 + 1]:off[f0 + 2]][pm["best_idx"][ia]])
     np.testing.assert_allclose(mx[:len(ia)], X, rtol=1e-4, atol=1e-4)
-    _assert_tri_residual(oracle.projection_matrix(K, T0), oracle.projection_matrix(K, T1), uv[off[f0]:off[f0 + 1]][ia],
-                         uv[off[f0 + 1]:off[f0 + 2]][pm["best_idx"][ia]], mx[:len(ia)],
-                         "segment at frame %d, bootstrap" % f0)
+    res = _assert_tri_residual(oracle.projection_matrix(K, T0), oracle.projection_matrix(K, T1),
+                               uv[off[f0]:off[f0 + 1]][ia], uv[off[f0 + 1]:off[f0 + 2]][pm["best_idx"][ia]], mx[:len(ia)],
+                               "segment at frame %d, bootstrap" % f0)
     np.testing.assert_array_equal(poses[0], np.asarray(T0, np.float32))
-    worst, rel = _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, mx, md)
+    if stats is not None:
+        stats["res"] = res
+    worst, rel = _teacher_forced(oracle, K, off, uv, desc, f0, poses, rec, mx, md, stats)
+    if stats is not None:
+        stats["pose"] = worst
     print("VO_TRI segment at frame %d: %d map points inside the residual bound" % (f0, len(mx)))
     assert worst < POSE_TOL, worst
     assert np.quantile(rel, 0.99) < 1e-4 and rel.max() < 1e-2, (np.quantile(rel, 0.99), rel.max())
