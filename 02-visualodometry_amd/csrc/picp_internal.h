@@ -186,3 +186,42 @@ struct VoArgs {     // by value; every pointer is device memory
   float* map_n1;
   float* map_n2;
 };
+
+// ---------------------------------------------------------------------------------------
+// observation tracks of the VO sequence (picp_vo_tracks.hip), by value
+// What a run records with the track log on: vo_tracklog_kernel after every append.
+struct VoTrackLog {
+  int32_t* mlog;           // per segment, dense: for observation i of frame f0+t+1 the accepted map
+                           // index or -1, at log_off[s] + (frame_off[f0+t+1] - frame_off[f0+1]) + i
+  const int64_t* log_off;  // per segment
+  int32_t* cre_c;          // per map slot: the step that created the point (bootstrap: 0), ...
+  int32_t* cre_x;          // ... its observation x in frame f0+c and ...
+  int32_t* cre_y;          // ... y in frame f0+c+1 (indices in the frame)
+};
+
+// The CSR build after a run: points are packed segment-major (segment s at pt_base[s], its used
+// map prefix only).
+struct VoTrackCsr {
+  VoTrackLog L;
+  const int64_t* frame_off;
+  const float2* uv;
+  const VoSegment* segs;
+  const float* map_xyz;
+  const float* poses;       // 16 per slot, camera-in-world
+  const int64_t* pt_base;   // n_seg + 1
+  int32_t* cnt;             // per point: matches counted, then the fill's cursor
+  int64_t* rel;             // per point: exclusive scan of the track lengths inside its segment
+  int64_t* seg_tot;         // per segment: its observations
+  const int64_t* seg_base;  // per segment: first observation (host prefix of seg_tot)
+  int64_t* track_off;       // n_points + 1
+  int64_t* obs_index;       // per observation: global observation index
+  int32_t* obs_slot;        // pose slot inside the segment
+  int32_t* obs_pose;        // slot0 + obs_slot
+  float2* obs_uv;
+  float* xyz0;              // the packed map, 3 per point
+  float* pose_wc;           // 16 per slot, world-in-camera
+  RefinePose* rposes;       // the refiner's table of the same poses
+  int64_t n_points, n_obs, n_slots;
+  int32_t n_seg, max_steps;
+  int64_t max_pts;          // the largest segment map
+};

@@ -51,6 +51,14 @@ hipError_t picp_launch_vo_block(hipStream_t stream, const VoArgs* a, int t, int 
 hipError_t picp_launch_vo_gather(hipStream_t stream, const VoArgs* a, int t);
 hipError_t picp_launch_vo_append(hipStream_t stream, const VoArgs* a, int t);
 
+// ---- picp_vo_tracks.hip
+// the track log of step t's append (t < 0: the bootstrap's), after it on the same stream
+hipError_t picp_launch_vo_tracklog(hipStream_t stream, const VoArgs* a, int t, const VoTrackLog* L);
+// the CSR build in two parts: counts and per-segment scan (cnt zeroed by the caller; then seg_tot
+// is read and seg_base, n_obs and the observation arrays are set), and everything else
+hipError_t picp_launch_vo_tracks_count(hipStream_t stream, const VoTrackCsr* B);
+hipError_t picp_launch_vo_tracks_fill(hipStream_t stream, const VoTrackCsr* B);
+
 // ---- picp_classify.hip
 int picp_classify_tile(void);
 hipError_t picp_launch_classify(hipStream_t stream, int nb, int np, const float* X, const float* Y,

@@ -52,6 +52,8 @@ EXPORTED = [
     "picp_refine_params_default", "picp_refine_create", "picp_refine_destroy", "picp_refine_set_poses",
     "picp_refine_set_tracks", "picp_refine_set_points", "picp_refine_run", "picp_refine_get_points",
     "picp_refine_get_stats", "picp_refine_time",
+    "picp_vo_set_track_log", "picp_vo_get_tracks", "picp_vo_get_poses_wc", "picp_vo_refine_map",
+    "picp_vo_get_refined_map", "picp_vo_refine_time",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -190,6 +192,13 @@ def lib():
         "picp_refine_get_points": ([vp, fp], i),
         "picp_refine_get_stats": ([vp, sp], i),
         "picp_refine_time": ([vp, pp, i, fp], i),
+        "picp_vo_set_track_log": ([vp, i], i),
+        "picp_vo_get_tracks": ([vp, i, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64),
+                                ctypes.POINTER(i64), ctypes.POINTER(i64)], i),
+        "picp_vo_get_poses_wc": ([vp, fp], i),
+        "picp_vo_refine_map": ([vp, pp], i),
+        "picp_vo_get_refined_map": ([vp, i, i64, fp, sp, ctypes.POINTER(i64)], i),
+        "picp_vo_refine_time": ([vp, pp, i, fp, fp], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -763,6 +772,58 @@ class VOSequence:
         ni = np.zeros(max(n.value, 1), np.int32)
         _check(lib().picp_vo_get_map_stats(self._h, seg, n.value, _i32ptr(nm), _i32ptr(ni), ctypes.byref(n)))
         return nm[:n.value], ni[:n.value]
+
+    def track_log(self, enable=True):
+        """Switch the recording of observation tracks (off by default); takes effect at the next run."""
+        _check(lib().picp_vo_set_track_log(self._h, int(bool(enable))))
+
+    def tracks(self, seg):
+        """(track_off, obs_slot, obs_index) of segment seg after a run with the track log on: map
+        point j (in map(seg)'s order) owns entries [track_off[j], track_off[j+1]) of obs_slot (the
+        pose slot inside the segment) and obs_index (the index into the uv / desc arrays the
+        sequence was created from), ascending by obs_index.  Raises PicpError(ERR_STATE) with the
+        log off or before a run."""
+        n, m = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().picp_vo_get_tracks(self._h, seg, None, None, None, ctypes.byref(n), ctypes.byref(m)))
+        off = np.zeros(n.value + 1, np.int64)
+        slot = np.zeros(max(m.value, 1), np.int32)
+        idx = np.zeros(max(m.value, 1), np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(lib().picp_vo_get_tracks(self._h, seg, off.ctypes.data_as(i64p), _i32ptr(slot),
+                                        idx.ctypes.data_as(i64p), ctypes.byref(n), ctypes.byref(m)))
+        return off, slot[:m.value], idx[:m.value]
+
+    def poses_wc(self):
+        """list over segments of (steps+1, 4, 4) world-in-camera poses: the table refine_map uses
+        (the float32 rigid inverse of poses())."""
+        n = int((self.steps + 1).sum())
+        out = np.zeros(16 * n, np.float32)
+        _check(lib().picp_vo_get_poses_wc(self._h, _fptr(out)))
+        return self._split(np.transpose(out.reshape(n, 4, 4), (0, 2, 1)).copy())
+
+    def refine_map(self, **params):
+        """Refine every segment's map against its tracks with the poses fixed (PointRefiner's kernel
+        and parameters); read the result with refined_map.  The map itself is not changed."""
+        prm = default_refine_params(**params)
+        _check(lib().picp_vo_refine_map(self._h, ctypes.byref(prm)))
+
+    def refined_map(self, seg):
+        """(xyz (n, 3), stats) of segment seg after refine_map; stats as PointRefiner.stats()."""
+        n = ctypes.c_int64()
+        _check(lib().picp_vo_get_refined_map(self._h, seg, 0, None, None, ctypes.byref(n)))
+        xyz = np.zeros((max(n.value, 1), 3), np.float32)
+        st = (Stats * max(n.value, 1))()
+        _check(lib().picp_vo_get_refined_map(self._h, seg, n.value, _fptr(xyz), st, ctypes.byref(n)))
+        rec = np.frombuffer(st, dtype=np.dtype([(k, np.float32 if t is ctypes.c_float else np.int32)
+                                                for k, t in Stats._fields_]), count=n.value)
+        return xyz[:n.value], {k: rec[k].copy() for k, _ in Stats._fields_ if k != "reserved"}
+
+    def refine_time(self, reps, **params):
+        """Mean device time in us of (the CSR build, the refine launch) over reps repetitions."""
+        prm = default_refine_params(**params)
+        b, r = ctypes.c_float(0), ctypes.c_float(0)
+        _check(lib().picp_vo_refine_time(self._h, ctypes.byref(prm), reps, ctypes.byref(b), ctypes.byref(r)))
+        return b.value, r.value
 
     def map(self, seg):
         n = ctypes.c_int64()

@@ -438,6 +438,50 @@ int picp_vo_get_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, float* desc,
 int picp_vo_set_track_stats(picp_vo_t* h, int enable);
 int picp_vo_get_map_stats(picp_vo_t* h, int seg, int64_t cap,
                           int32_t* n_matched, int32_t* n_inlier, int64_t* n);
+/* Observation tracks of a run, off by default; read-only like the track counters (poses, step
+ * records and maps keep their bits).  May be switched any time before a run.  With the log on, a
+ * run records on the device which observation matched which map point; afterwards the tracks are
+ * built on the device in the refiner's CSR form (picp_refine_set_tracks), lazily at the first call
+ * that needs them.
+ * The track of map point j of segment seg (picp_vo_get_map's order): the point was created from
+ * the pair (x in frame first+c, y in frame first+c+1), c = 0 for a bootstrap point and c = t for a
+ * point appended by step t.  Its track holds x, y, and every accepted frame->map match of the
+ * segment whose best index is j except the match whose observation is y itself (step 0 matches
+ * frame first+1 against the bootstrap map and usually finds the observation that created the
+ * point; it does not count twice).  Several observations of one frame matching one point all
+ * stay.  Ascending by global observation index (inside a segment: by slot, then by index in the
+ * frame); the same from run to run and under every schedule.
+ * Slots: slot 0's pose is the first bootstrap pose; the second bootstrap pose is in no slot, as in
+ * the reference (exec/icp_test.cpp keeps T0 only); slot 1 is step 0's estimate.
+ * PICP_ERR_STATE: the log is off, or no run has completed since it was switched on or since the
+ * last picp_vo_set_segments.  PICP_ERR_ARG: null handle, segment out of range, or more than
+ * INT32_MAX observations in all tracks. */
+int picp_vo_set_track_log(picp_vo_t* h, int enable);
+/* Segment seg's tracks: point j owns entries [track_off[j], track_off[j+1]) of obs_slot (the pose
+ * slot inside the segment, 0..steps) and obs_index (the global observation index into the uv /
+ * desc arrays given to picp_vo_create).  Arrays nullable; a call with all arrays NULL returns
+ * *n_points (= the map size) and *n_obs.  Non-null arrays must hold n_points+1 / n_obs / n_obs
+ * entries. */
+int picp_vo_get_tracks(picp_vo_t* h, int seg, int64_t* track_off, int32_t* obs_slot,
+                       int64_t* obs_index, int64_t* n_points, int64_t* n_obs);
+/* The pose table the refinement uses: sum(steps+1) WORLD-IN-CAMERA 4x4, column-major,
+ * segment-major like picp_vo_get_poses.  Slot k's entry is the float32 rigid inverse
+ * (R^T, -(R^T t) summed left to right, no fused multiply-add) of the pose picp_vo_get_poses
+ * reports for that slot.  Same state conditions as picp_vo_get_tracks. */
+int picp_vo_get_poses_wc(picp_vo_t* h, float* T_wc);
+/* Structure-only refinement of every segment's map against its tracks with the poses fixed: one
+ * launch of the picp_refine_* kernel over all segments' points (bit-equal to picp_refine_run on
+ * the same tracks, poses and points).  prm NULL = picp_refine_params_default.  Blocking.  Starts
+ * from the run's map every time (a second call repeats the first); the map, poses, step records
+ * and any later picp_vo_run keep their bits.
+ * picp_vo_get_refined_map: as picp_vo_get_map (xyz / stats nullable; stats as
+ * picp_refine_get_stats); PICP_ERR_STATE before any picp_vo_refine_map since the last run. */
+int picp_vo_refine_map(picp_vo_t* h, const picp_refine_params* prm);
+int picp_vo_get_refined_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, picp_stats* stats, int64_t* n);
+/* Diagnostic: mean device time (us) over reps >= 1 of (a) the CSR build and (b) the refine launch,
+ * HIP events around the kernels only.  Leaves the results of one picp_vo_refine_map. */
+int picp_vo_refine_time(picp_vo_t* h, const picp_refine_params* prm, int reps,
+                        float* build_us, float* refine_us);
 /* mean device time of `reps` back-to-back runs (HIP events on the handle's stream) */
 int picp_vo_time(picp_vo_t* h, int reps, float* ms_per_run);
 int picp_vo_info(picp_vo_t* h, int64_t* n_obs, int64_t* n_slots, int64_t* map_slots, int* npt);
