@@ -13,6 +13,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "picp_c.h"        // picp_stats
 #include "picp_problem.h"  // PICP_BLOCK, PICP_NPART, PICP_POSE_SETS, PicpProblem
 
 // partial slot layout
@@ -81,6 +82,41 @@ struct RefineArgs {
 // one world-in-camera pose of the refiner's table: the rows of [R | t], 48 B (three 16-B loads)
 struct RefinePose {
   float4 r0, r1, r2;     // (r00 r01 r02 t0), (r10 r11 r12 t1), (r20 r21 r22 t2)
+};
+
+// alternating adjustment (picp_adjust.hip), by value; every pointer is device memory
+// The build of the pose-major view of the refiner's point-major tracks.
+struct AdjView {
+  const int64_t* track_off;  // n_points + 1
+  const int32_t* obs_pose;   // per observation (source position)
+  const float2* obs_uv;
+  int32_t* cnt;              // per pose: observations counted, then the fill's cursor
+  int64_t* pose_off;         // n_poses + 1
+  int2* tmp;                 // per entry, as the cursors placed it: (source position, point)
+  int32_t* view_point;       // per entry, canonical order
+  float2* view_uv;
+  int64_t n_points, n_obs;
+  int32_t n_poses, pad;
+};
+
+// One pose step: problem p of the batch is pose movable[p].
+struct AdjPose {
+  const int32_t* movable;    // n_problems
+  const int64_t* pose_off;
+  const int64_t* plane_off;  // n_problems: the batch's plane offsets
+  const int32_t* view_point;
+  const float2* view_uv;
+  const float* xyz;          // the current points
+  float* X;                  // the batch's SoA planes
+  float* Y;
+  float* Z;
+  float* U;
+  float* V;
+  PicpState* init;           // the batch's initial states
+  RefinePose* rposes;        // the refiner's pose rows
+  float* T;                  // the poses as 4x4, 16 floats each
+  picp_stats* pose_stats;    // n_poses
+  int32_t n_problems, pad;
 };
 
 static_assert(sizeof(RefinePose) == 48, "RefinePose must be 48 B");

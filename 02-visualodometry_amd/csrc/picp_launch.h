@@ -75,6 +75,17 @@ hipError_t picp_launch_refine(hipStream_t stream, const RefineArgs* a, const Ref
                               const int64_t* track_off, const int32_t* obs_pose, const float2* obs_uv,
                               float* xyz, picp_stats* stats);
 
+// ---- picp_adjust.hip
+// the pose-major view of the tracks: count, scan, fill, rank (cnt zeroed by the caller)
+hipError_t picp_launch_adjust_view(hipStream_t stream, const AdjView* v);
+int picp_adjust_rank_tile(void);
+// the current points (write_uv: and the pixels) into the batch's planes, the poses into its initial states
+hipError_t picp_launch_adjust_gather(hipStream_t stream, const AdjPose* g, int write_uv);
+// the solved states `st` (n_problems) into the refiner's poses and pose stats (zeroed by the caller)
+hipError_t picp_launch_adjust_writeback(hipStream_t stream, const AdjPose* g, const PicpState* st);
+hipError_t picp_launch_adjust_sums(hipStream_t stream, const picp_stats* point_stats, int64_t n_points,
+                                   const picp_stats* pose_stats, int64_t n_poses, picp_adjust_sweep* out);
+
 // ---- picp_essential.hip
 hipError_t picp_launch_essential(hipStream_t stream, const EssArgs* args, const int64_t* offs, const float* p1,
                                  const float* p2, int32_t* idx, double* Es, int32_t* ns, int32_t* cnt,

@@ -11,32 +11,9 @@
 #include "picp_c.h"
 #include "picp_host.h"
 #include "picp_launch.h"
+#include "picp_refine_host.h"
 
 #define set_err picp_set_err
-
-struct picp_refine {
-  int device = 0, rows = 0, cols = 0;
-  float K[9];
-  hipStream_t stream = nullptr;
-  RefinePose* poses_d = nullptr;
-  int64_t cap_poses = 0;
-  int n_poses = -1;              // -1: not set
-  int64_t* off_d = nullptr;
-  int64_t cap_off = 0;
-  int32_t* obs_pose_d = nullptr;
-  int64_t cap_obs_pose = 0;
-  float2* obs_uv_d = nullptr;
-  int64_t cap_obs_uv = 0;
-  int64_t n_points = -1, n_obs = 0;  // -1: tracks not set
-  int32_t max_pose_idx = -1;     // largest pose index of the tracks (-1: no observation)
-  float* xyz_d = nullptr;        // the current points
-  int64_t cap_xyz = 0;
-  float* xyz0_d = nullptr;       // picp_refine_time: the points the call found
-  int64_t cap_xyz0 = 0;
-  picp_stats* stats_d = nullptr;
-  int64_t cap_stats = 0;
-  bool have_points = false, have_stats = false;
-};
 
 extern "C" void picp_refine_params_default(picp_refine_params* p) {
   if (!p) return;
@@ -73,6 +50,7 @@ extern "C" int picp_refine_destroy(picp_refine_t* h) {
   if (!h) return PICP_OK;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
+  adjust_free(h);
   void* bufs[] = {h->poses_d, h->off_d, h->obs_pose_d, h->obs_uv_d, h->xyz_d, h->xyz0_d, h->stats_d};
   for (void* p : bufs)
     if (p) hipFree(p);
@@ -94,12 +72,16 @@ extern "C" int picp_refine_set_poses(picp_refine_t* h, const float* T_wc, int n_
     tab[k].r2 = make_float4(T[2], T[6], T[10], T[14]);
   }
   int rc = grow((void**)&h->poses_d, &h->cap_poses, n_poses, sizeof(RefinePose));
+  if (!rc) rc = grow((void**)&h->adj.T_d, &h->adj.cap_T, 16 * (int64_t)n_poses, sizeof(float));
   if (rc) return rc;
   if (n_poses) {
     HIP_TRY(hipMemcpyAsync(h->poses_d, tab.data(), (size_t)n_poses * sizeof(RefinePose), hipMemcpyHostToDevice, h->stream));
+    // the same poses as given: picp_refine_get_poses returns a pose that never moved with these bits
+    HIP_TRY(hipMemcpyAsync(h->adj.T_d, T_wc, (size_t)n_poses * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   h->n_poses = n_poses;
+  adjust_poses_changed(h);
   return PICP_OK;
 }
 
@@ -142,6 +124,7 @@ extern "C" int picp_refine_set_tracks(picp_refine_t* h, int64_t n_points, const 
   h->max_pose_idx = max_idx;
   if (old_points != n_points) h->have_points = false;
   h->have_stats = false;
+  adjust_tracks_changed(h);
   return PICP_OK;
 }
 
@@ -162,7 +145,7 @@ extern "C" int picp_refine_set_points(picp_refine_t* h, const float* xyz) {
 }
 
 // everything a launch needs is set and consistent; fills the by-value arguments
-static int refine_prepare(picp_refine* h, const picp_refine_params* prm, RefineArgs* a) {
+int refine_prepare(picp_refine* h, const picp_refine_params* prm, RefineArgs* a) {
   CHECK_ARG(!(prm->threshold != prm->threshold) && !(prm->damping != prm->damping), "refine: NaN parameter");
   CHECK_ARG(prm->max_rounds >= 0, "refine: max_rounds must not be negative");
   if (h->n_poses < 0) return set_err(PICP_ERR_STATE, "refine: poses not set");
@@ -188,7 +171,7 @@ static int refine_prepare(picp_refine* h, const picp_refine_params* prm, RefineA
   return PICP_OK;
 }
 
-static hipError_t refine_enqueue(picp_refine* h, const RefineArgs* a) {
+hipError_t refine_enqueue(picp_refine* h, const RefineArgs* a) {
   return picp_launch_refine(h->stream, a, h->poses_d, h->off_d, h->obs_pose_d, h->obs_uv_d, h->xyz_d, h->stats_d);
 }
 

@@ -25,6 +25,7 @@
 #include "picp_host.h"
 #include "picp_internal.h"
 #include "picp_launch.h"
+#include "picp_refine_host.h"
 
 static_assert(sizeof(picp_vo_step) == sizeof(VoStep), "picp_vo_step must mirror VoStep");
 
@@ -151,6 +152,10 @@ struct picp_vo {
   std::vector<int64_t> pt_base, obs_base;  // per segment (+1): first point / first observation of the CSR
   float* xyz_ref = nullptr;                // picp_vo_refine_map's result
   picp_stats* stats_ref = nullptr;
+  // picp_vo_adjust: a refiner of its own, loaded from the CSR build on the device (its buffers are
+  // its own: the adjustment writes nothing of the run's or of picp_vo_refine_map's)
+  picp_refine* adj = nullptr;
+  bool adj_tracks = false, adjusted = false;  // adj holds this build's tracks / an adjustment of it
   bool guard = false;
   std::vector<VoGuarded> guards;
 #ifdef PICP_VO_DIAG
@@ -190,6 +195,7 @@ static void vo_tlog_free(picp_vo* h, bool release) {
   if (h->csr_b) vo_dfree(h, h->csr_b);
   h->csr_a = h->csr_b = nullptr;
   h->csr_built = h->refined = false;
+  h->adj_tracks = h->adjusted = false;
   h->xyz_ref = nullptr;
   h->stats_ref = nullptr;
   if (!release) return;
@@ -217,6 +223,8 @@ extern "C" int picp_vo_destroy(picp_vo_t* h) {
   if (!h) return PICP_OK;
   if (h->stream) hipStreamSynchronize(h->stream);
   vo_free_segments(h);
+  if (h->adj) picp_refine_destroy(h->adj);
+  h->adj = nullptr;
   void* bufs[] = {h->frame_off_d, h->uv_d, h->desc_d, h->pm_bi, h->pm_acc, h->wm_bi, h->wm_acc,
                   h->pm_bd, h->pm_sd, h->wm_bd, h->wm_sd, h->obs_h, h->obs_n1, h->obs_n2, h->track_d};
   for (void* p : bufs)
@@ -1327,5 +1335,66 @@ extern "C" int picp_vo_refine_time(picp_vo_t* h, const picp_refine_params* prm, 
   *build_us = (float)(1000.0 * tb / reps);
   *refine_us = (float)(1000.0 * tr / reps);
   h->refined = true;
+  return PICP_OK;
+}
+
+// ---- alternating adjustment of the run's poses and maps (picp_adjust_runtime.cpp)
+
+extern "C" int picp_vo_adjust(picp_vo_t* h, const picp_adjust_params* prm) {
+  CHECK_ARG(h, "picp_vo_adjust: null handle");
+  int rc = vo_tracks_ready(h, "picp_vo_adjust");
+  if (rc == PICP_OK) rc = vo_tracks_build(h);
+  if (rc != PICP_OK) return rc;
+  picp_adjust_params def;
+  if (!prm) {
+    picp_adjust_params_default(&def);
+    prm = &def;
+  }
+  CHECK_ARG(prm->sweeps >= 0, "picp_vo_adjust: sweeps must not be negative");  // before anything is copied
+  if (!h->adj) {
+    rc = picp_refine_create(&h->adj, h->device, h->rows, h->cols, h->K);
+    if (rc != PICP_OK) return rc;
+  }
+  h->adjusted = false;
+  // from the run's map and poses every time; the tracks once per build
+  const VoTrackCsr& B = h->csr;
+  rc = refine_load_device(h->adj, (int)h->n_slots, B.rposes, B.pose_wc, !h->adj_tracks, B.n_points, B.n_obs,
+                          B.track_off, B.obs_pose, B.obs_uv, B.xyz0);
+  if (rc != PICP_OK) return rc;
+  h->adj_tracks = true;
+  // slot 0 of every segment is its world frame
+  std::vector<uint8_t> fixed((size_t)h->n_slots, 0);
+  for (int s = 0; s < h->n_seg; ++s) fixed[(size_t)h->segs[(size_t)s].slot0] = 1;
+  rc = picp_refine_set_fixed_poses(h->adj, fixed.data());
+  if (rc == PICP_OK) rc = picp_refine_adjust(h->adj, prm);
+  if (rc != PICP_OK) return rc;
+  h->adjusted = true;
+  return PICP_OK;
+}
+
+extern "C" int picp_vo_get_adjusted_poses_wc(picp_vo_t* h, float* T_wc) {
+  CHECK_ARG(h && T_wc, "picp_vo_get_adjusted_poses_wc: null argument");
+  if (!h->adjusted || !h->csr_built)
+    return picp_set_err(PICP_ERR_STATE, "picp_vo_get_adjusted_poses_wc: no picp_vo_adjust since the last run");
+  return picp_refine_get_poses(h->adj, T_wc);
+}
+
+extern "C" int picp_vo_get_adjusted_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, picp_stats* stats,
+                                        int64_t* n) {
+  CHECK_ARG(h && n, "picp_vo_get_adjusted_map: null argument");
+  if (!h->adjusted || !h->csr_built)
+    return picp_set_err(PICP_ERR_STATE, "picp_vo_get_adjusted_map: no picp_vo_adjust since the last run");
+  CHECK_ARG(seg >= 0 && seg < h->n_seg, "picp_vo_get_adjusted_map: segment out of range");
+  HIP_TRY(hipSetDevice(h->device));
+  const int64_t p0 = h->pt_base[seg], np = h->pt_base[seg + 1] - p0;
+  *n = np;
+  const int64_t k = std::min(np, std::max<int64_t>(cap, 0));
+  // picp_refine_adjust returned: the refiner's stream is idle
+  if (xyz && k)
+    HIP_TRY(hipMemcpy(xyz, h->adj->xyz_d + 3 * p0, (size_t)k * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (stats && k) {
+    if (!h->adj->have_stats) memset(stats, 0, (size_t)k * sizeof(picp_stats));  // sweeps == 0: no point step
+    else HIP_TRY(hipMemcpy(stats, h->adj->stats_d + p0, (size_t)k * sizeof(picp_stats), hipMemcpyDeviceToHost));
+  }
   return PICP_OK;
 }

@@ -54,6 +54,9 @@ EXPORTED = [
     "picp_refine_get_stats", "picp_refine_time",
     "picp_vo_set_track_log", "picp_vo_get_tracks", "picp_vo_get_poses_wc", "picp_vo_refine_map",
     "picp_vo_get_refined_map", "picp_vo_refine_time",
+    "picp_adjust_params_default", "picp_refine_set_fixed_poses", "picp_refine_run_poses", "picp_refine_adjust",
+    "picp_refine_get_poses", "picp_refine_get_pose_stats", "picp_refine_get_pose_view", "picp_refine_get_sweeps",
+    "picp_refine_adjust_time", "picp_vo_adjust", "picp_vo_get_adjusted_poses_wc", "picp_vo_get_adjusted_map",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -86,6 +89,21 @@ class Params(ctypes.Structure):
     _fields_ = [("threshold", ctypes.c_float), ("damping", ctypes.c_float),
                 ("min_inliers", ctypes.c_int32), ("keep_outliers", ctypes.c_int32),
                 ("max_rounds", ctypes.c_int32), ("conv_eps", ctypes.c_float)]
+
+
+class AdjustParams(ctypes.Structure):
+    """picp_adjust_params: the point step's parameters, the pose step's, and the sweeps."""
+    _fields_ = [("points", Params), ("poses", Params), ("sweeps", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AdjustSweep(ctypes.Structure):
+    """picp_adjust_sweep: the sums of one sweep's per-point and per-pose stats."""
+    _fields_ = [("chi_in_points", ctypes.c_double), ("chi_in_poses", ctypes.c_double),
+                ("n_in_points", ctypes.c_int64), ("n_in_poses", ctypes.c_int64),
+                ("ok_points", ctypes.c_int64), ("ok_poses", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -199,6 +217,18 @@ def lib():
         "picp_vo_refine_map": ([vp, pp], i),
         "picp_vo_get_refined_map": ([vp, i, i64, fp, sp, ctypes.POINTER(i64)], i),
         "picp_vo_refine_time": ([vp, pp, i, fp, fp], i),
+        "picp_adjust_params_default": ([ctypes.POINTER(AdjustParams)], None),
+        "picp_refine_set_fixed_poses": ([vp, ctypes.POINTER(ctypes.c_uint8)], i),
+        "picp_refine_run_poses": ([vp, pp], i),
+        "picp_refine_adjust": ([vp, ctypes.POINTER(AdjustParams)], i),
+        "picp_refine_get_poses": ([vp, fp], i),
+        "picp_refine_get_pose_stats": ([vp, sp], i),
+        "picp_refine_get_pose_view": ([vp, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32), fp], i),
+        "picp_refine_get_sweeps": ([vp, ctypes.POINTER(AdjustSweep), i, ctypes.POINTER(i)], i),
+        "picp_refine_adjust_time": ([vp, ctypes.POINTER(AdjustParams), i, fp, fp, fp, fp], i),
+        "picp_vo_adjust": ([vp, ctypes.POINTER(AdjustParams)], i),
+        "picp_vo_get_adjusted_poses_wc": ([vp, fp], i),
+        "picp_vo_get_adjusted_map": ([vp, i, i64, fp, sp, ctypes.POINTER(i64)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -825,6 +855,29 @@ class VOSequence:
         _check(lib().picp_vo_refine_time(self._h, ctypes.byref(prm), reps, ctypes.byref(b), ctypes.byref(r)))
         return b.value, r.value
 
+    def adjust(self, sweeps=None, points=None, poses=None):
+        """Alternating adjustment of every segment's poses and map on the run's tracks, slot 0 of
+        every segment fixed (PointRefiner.adjust's arguments); read the result with
+        adjusted_poses_wc and adjusted_map.  The run's own poses and map are not changed."""
+        prm = default_adjust_params(sweeps=sweeps, points=points, poses=poses)
+        _check(lib().picp_vo_adjust(self._h, ctypes.byref(prm)))
+
+    def adjusted_poses_wc(self):
+        """list over segments of (steps+1, 4, 4) world-in-camera poses after adjust (poses_wc's layout)."""
+        n = int((self.steps + 1).sum())
+        out = np.zeros(16 * n, np.float32)
+        _check(lib().picp_vo_get_adjusted_poses_wc(self._h, _fptr(out)))
+        return self._split(np.transpose(out.reshape(n, 4, 4), (0, 2, 1)).copy())
+
+    def adjusted_map(self, seg):
+        """(xyz (n, 3), stats) of segment seg after adjust; stats as PointRefiner.stats()."""
+        n = ctypes.c_int64()
+        _check(lib().picp_vo_get_adjusted_map(self._h, seg, 0, None, None, ctypes.byref(n)))
+        xyz = np.zeros((max(n.value, 1), 3), np.float32)
+        st = (Stats * max(n.value, 1))()
+        _check(lib().picp_vo_get_adjusted_map(self._h, seg, n.value, _fptr(xyz), st, ctypes.byref(n)))
+        return xyz[:n.value], _stats_arrays(st, n.value)
+
     def map(self, seg):
         n = ctypes.c_int64()
         _check(lib().picp_vo_get_map(self._h, seg, 0, None, None, ctypes.byref(n)))
@@ -844,6 +897,34 @@ def default_refine_params(**kw):
     return p
 
 
+def _stats_arrays(st, n):
+    """A ctypes array of Stats -> dict of per-item numpy arrays."""
+    rec = np.frombuffer(st, dtype=np.dtype([(k, np.float32 if t is ctypes.c_float else np.int32)
+                                            for k, t in Stats._fields_]), count=n)
+    return {k: rec[k].copy() for k, _ in Stats._fields_ if k != "reserved"}
+
+
+def default_adjust_params(sweeps=None, points=None, poses=None):
+    """picp_adjust_params: points (picp_refine_params fields) and poses (picp_params fields) are
+    dicts of overrides of the defaults (the refiner's; the solver's with threshold 3000); sweeps 3."""
+    p = AdjustParams()
+    lib().picp_adjust_params_default(ctypes.byref(p))
+    for k, v in (points or {}).items():
+        setattr(p.points, k, v)
+    for k, v in (poses or {}).items():
+        setattr(p.poses, k, v)
+    if sweeps is not None:
+        p.sweeps = sweeps
+    return p
+
+
+def adjust_rank_tile():
+    """Entries the view build's rank kernel stages per LDS tile (tests pick list lengths around it)."""
+    fn = lib().picp_adjust_rank_tile
+    fn.restype = ctypes.c_int
+    return fn()
+
+
 class PointRefiner:
     """picp_refine_t: refine map points against all of their observations with the poses held
     fixed (structure-only Gauss-Newton, csrc/picp_refine.hip).  Poses, tracks and points stay on
@@ -853,6 +934,7 @@ class PointRefiner:
         self._h = ctypes.c_void_p()
         self.device = device
         self.n_points = None
+        self.n_poses = None
         _check(lib().picp_refine_create(ctypes.byref(self._h), device, rows, cols, _fptr(k_to_c(K))))
 
     def close(self):
@@ -871,6 +953,7 @@ class PointRefiner:
         Ts = np.asarray(Ts, np.float32).reshape(-1, 4, 4)
         flat = np.ascontiguousarray(np.transpose(Ts, (0, 2, 1)).reshape(-1))
         _check(lib().picp_refine_set_poses(self._h, _fptr(flat) if flat.size else None, Ts.shape[0]))
+        self.n_poses = Ts.shape[0]
 
     def set_tracks(self, track_off, obs_pose, obs_uv):
         """CSR tracks: point i owns observations [track_off[i], track_off[i+1]) of obs_pose (pose
@@ -915,6 +998,69 @@ class PointRefiner:
         us = ctypes.c_float(0)
         _check(lib().picp_refine_time(self._h, ctypes.byref(prm), reps, ctypes.byref(us)))
         return us.value
+
+    # --- alternating adjustment (picp_refine_run_poses, picp_refine_adjust) ---------------------
+    def set_fixed_poses(self, fixed):
+        """(n_poses,) flags: a fixed pose never moves.  None: no pose is fixed."""
+        if fixed is None:
+            _check(lib().picp_refine_set_fixed_poses(self._h, None))
+            return
+        m = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+        assert self.n_poses is None or m.size == self.n_poses
+        _check(lib().picp_refine_set_fixed_poses(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+
+    def poses(self):
+        """(n_poses, 4, 4) current world-in-camera poses."""
+        n = self.n_poses or 0
+        out = np.zeros(16 * n, np.float32)
+        _check(lib().picp_refine_get_poses(self._h, _fptr(out) if n else None))
+        return np.transpose(out.reshape(n, 4, 4), (0, 2, 1)).copy()
+
+    def pose_stats(self):
+        """dict of per-pose arrays of the last pose step (all zero for fixed and unobserved poses)."""
+        n = self.n_poses or 0
+        st = (Stats * max(n, 1))()
+        _check(lib().picp_refine_get_pose_stats(self._h, st))
+        return _stats_arrays(st, n)
+
+    def pose_view(self):
+        """The pose-major view of the tracks: (pose_off (n_poses+1,), obs_point, obs_uv (n_obs, 2));
+        pose k owns entries [pose_off[k], pose_off[k+1]) in ascending position of the point-major arrays."""
+        n = self.n_poses or 0
+        off = np.zeros(n + 1, np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(lib().picp_refine_get_pose_view(self._h, off.ctypes.data_as(i64p), None, None))
+        m = int(off[-1])
+        pt = np.zeros(max(m, 1), np.int32)
+        uv = np.zeros((max(m, 1), 2), np.float32)
+        _check(lib().picp_refine_get_pose_view(self._h, off.ctypes.data_as(i64p), _i32ptr(pt), _fptr(uv)))
+        return off, pt[:m], uv[:m]
+
+    def run_poses(self, **params):
+        """One pose step (picp_batch_solve's parameters) -> (poses (n, 4, 4), pose stats)."""
+        prm = default_params(**params)
+        _check(lib().picp_refine_run_poses(self._h, ctypes.byref(prm)))
+        return self.poses(), self.pose_stats()
+
+    def adjust(self, sweeps=None, points=None, poses=None):
+        """sweeps x (point step, pose step); points / poses: dicts of parameter overrides."""
+        prm = default_adjust_params(sweeps=sweeps, points=points, poses=poses)
+        _check(lib().picp_refine_adjust(self._h, ctypes.byref(prm)))
+
+    def sweeps(self):
+        """list of dicts, one per sweep of the last adjust: the sums of the steps' stats."""
+        n = ctypes.c_int(0)
+        _check(lib().picp_refine_get_sweeps(self._h, None, 0, ctypes.byref(n)))
+        out = (AdjustSweep * max(n.value, 1))()
+        _check(lib().picp_refine_get_sweeps(self._h, out, n.value, ctypes.byref(n)))
+        return [out[k].as_dict() for k in range(n.value)]
+
+    def adjust_time(self, reps, sweeps=None, points=None, poses=None):
+        """Mean device times in us: (view build, and per sweep: gather + write-back, pose solve, point step)."""
+        prm = default_adjust_params(sweeps=sweeps, points=points, poses=poses)
+        t = [ctypes.c_float(0) for _ in range(4)]
+        _check(lib().picp_refine_adjust_time(self._h, ctypes.byref(prm), reps, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
 
 
 def refine_points(K, rows, cols, poses, track_off, obs_pose, obs_uv, xyz, device=0, **params):

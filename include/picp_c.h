@@ -325,6 +325,58 @@ int picp_refine_get_stats(picp_refine_t* h, picp_stats* stats /* n_points */);
  * found. */
 int picp_refine_time(picp_refine_t* h, const picp_refine_params* params, int reps, float* us_per_run);
 
+/* ---------------- alternating pose / point adjustment (resection, intersection, repeat) ---------------- */
+
+/* The refiner's poses can move too.  A POSE STEP solves, for every movable pose k (not fixed, and
+ * observed by at least one track), exactly the picp_batch_solve problem whose correspondences are
+ * the pose's observations (current point j, pixel) in CANONICAL ORDER -- ascending position in the
+ * arrays given to picp_refine_set_tracks: ascending point, then place in the track; a point observed
+ * twice by one pose appears twice -- from the handle's current pose, with a picp_params; problems in
+ * ascending pose order, laid out as a picp_batch of those sizes is.  A solved pose with a non-finite
+ * entry is not written back: the pose keeps its value and its stats get ok = 0.  Fixed poses and
+ * poses no track observes keep their bits and have all-zero stats.
+ * The pose-major view of the tracks is built on the device at the first call that needs it and
+ * dropped by picp_refine_set_tracks; the gather of the points into the solver's planes and the
+ * write-back of the solved poses are device kernels; the solve is the one host wait of a step.
+ * One SWEEP is a point step (picp_refine_run) followed by a pose step; picp_refine_adjust is exactly
+ * that sequence, `sweeps` times, and gives its bits.  Everything is bit-reproducible from run to run. */
+typedef struct picp_adjust_params {
+  picp_refine_params points;  /* point step: as picp_refine_run            */
+  picp_params poses;          /* pose step: as picp_batch_solve            */
+  int32_t sweeps;             /* default 3; 0 launches nothing             */
+  int32_t reserved;
+} picp_adjust_params;
+typedef struct picp_adjust_sweep {  /* one per sweep, in order */
+  double chi_in_points, chi_in_poses;   /* sums of the steps' per-item stats.chi_in */
+  int64_t n_in_points, n_in_poses, ok_points, ok_poses;
+} picp_adjust_sweep;
+/* points = picp_refine_params_default, poses = picp_params_default with threshold 3000 (the
+ * gate both steps share, exec/icp_test.cpp:86), sweeps = 3. */
+void picp_adjust_params_default(picp_adjust_params* p);
+/* fixed[k] != 0: pose k never moves.  NULL: none.  PICP_ERR_ARG before picp_refine_set_poses, which
+ * also resets the mask (and the sweep records). */
+int picp_refine_set_fixed_poses(picp_refine_t* h, const uint8_t* fixed /* n_poses; NULL: none */);
+/* PICP_ERR_STATE before poses, tracks or points were set; PICP_ERR_ARG on a NaN parameter or a
+ * negative sweeps / max_rounds; a failed call launches nothing.  Blocking. */
+int picp_refine_run_poses(picp_refine_t* h, const picp_params* params);
+int picp_refine_adjust(picp_refine_t* h, const picp_adjust_params* params);
+/* The current poses (column-major 4x4, world-in-camera; a pose that never moved has the bits it
+ * was set with) and the stats of the last pose step (PICP_ERR_STATE before one). */
+int picp_refine_get_poses(picp_refine_t* h, float* T_wc /* 16*n_poses */);
+int picp_refine_get_pose_stats(picp_refine_t* h, picp_stats* stats /* n_poses */);
+/* The pose-major view: pose k owns entries [pose_off[k], pose_off[k+1]) of obs_point (the owning
+ * point) and obs_uv (float2), in canonical order.  Arrays nullable; sizes n_poses+1 / n_obs / 2 n_obs. */
+int picp_refine_get_pose_view(picp_refine_t* h, int64_t* pose_off, int32_t* obs_point, float* obs_uv);
+/* The records of the last picp_refine_adjust: *n = its sweeps, the first min(n, cap) are copied.
+ * Summed on the device in a fixed order. */
+int picp_refine_get_sweeps(picp_refine_t* h, picp_adjust_sweep* out, int cap, int* n);
+/* Diagnostic: mean device time in us over reps of the view build (build_us, per build) and, per
+ * sweep, of the gather and write-back kernels (gather_us), the pose batch's solve with its result
+ * read-back (pose_us) and the point step (point_us).  Points and poses are restored before every
+ * repetition, outside the timed spans; leaves the results of one picp_refine_adjust. */
+int picp_refine_adjust_time(picp_refine_t* h, const picp_adjust_params* params, int reps,
+                            float* build_us, float* gather_us, float* pose_us, float* point_us);
+
 /* ---------------- descriptor matching (match_points replacement) ---------------- */
 
 /* src/my_utilities.h:70-120: for each of the n1 descriptors of set 1 (float[dim], packed) the
@@ -482,6 +534,19 @@ int picp_vo_get_refined_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, picp
  * HIP events around the kernels only.  Leaves the results of one picp_vo_refine_map. */
 int picp_vo_refine_time(picp_vo_t* h, const picp_refine_params* prm, int reps,
                         float* build_us, float* refine_us);
+/* Alternating adjustment of every segment's poses and map (picp_refine_adjust) on the tracks and
+ * the pose table of picp_vo_refine_map, with slot 0 of every segment fixed (the segment's world
+ * frame): bit-equal to picp_refine_adjust on a refiner given the same tracks, poses, points and
+ * mask.  prm NULL = picp_adjust_params_default.  Blocking.  Same state conditions as
+ * picp_vo_get_tracks.  Starts from the run's map and poses every time (a second call repeats the
+ * first); the run's map, poses and step records, any later picp_vo_run and any picp_vo_refine_map
+ * keep their bits.
+ * picp_vo_get_adjusted_poses_wc: the layout of picp_vo_get_poses_wc; picp_vo_get_adjusted_map: as
+ * picp_vo_get_refined_map (the stats of the last point step).  PICP_ERR_STATE before any
+ * picp_vo_adjust since the last run. */
+int picp_vo_adjust(picp_vo_t* h, const picp_adjust_params* prm);
+int picp_vo_get_adjusted_poses_wc(picp_vo_t* h, float* T_wc);
+int picp_vo_get_adjusted_map(picp_vo_t* h, int seg, int64_t cap, float* xyz, picp_stats* stats, int64_t* n);
 /* mean device time of `reps` back-to-back runs (HIP events on the handle's stream) */
 int picp_vo_time(picp_vo_t* h, int reps, float* ms_per_run);
 int picp_vo_info(picp_vo_t* h, int64_t* n_obs, int64_t* n_slots, int64_t* map_slots, int* npt);
