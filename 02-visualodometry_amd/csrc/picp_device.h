@@ -950,9 +950,23 @@ __device__ __forceinline__ void taylor_sincos(float a, float* s, float* c) {
 }
 
 // src/defs.h:100-136 v2tEuler's rotation: Rd = Rx(a)*Ry(b)*Rz(c) (float) of dx[3..5].
+// ONE_CMP: the range test as one compare, the unsigned maximum of the three |angle| bit patterns
+// against the bits of 0.0625 (positive floats order as their bits; a NaN's bits lie above every
+// finite value's, so it takes the libm path as it does with the three float compares), and the
+// Taylor path as the fall-through.  The same path for every input, so the same bits.
+template <bool ONE_CMP = false>
 __device__ __forceinline__ void update_rotation(const float dx[6], float Rd[3][3]) {
   float sa, ca, sb, cb, sc, cc;
-  if (fabsf(dx[3]) <= 0.0625f && fabsf(dx[4]) <= 0.0625f && fabsf(dx[5]) <= 0.0625f) {
+  bool small;
+  if constexpr (ONE_CMP) {
+    const unsigned a = __float_as_uint(dx[3]) & 0x7fffffffu, b = __float_as_uint(dx[4]) & 0x7fffffffu,
+                   c = __float_as_uint(dx[5]) & 0x7fffffffu;
+    const unsigned ab = a > b ? a : b;
+    small = __builtin_expect((ab > c ? ab : c) <= 0x3d800000u, 1);  // 0x3d800000: 0.0625f
+  } else {
+    small = fabsf(dx[3]) <= 0.0625f && fabsf(dx[4]) <= 0.0625f && fabsf(dx[5]) <= 0.0625f;
+  }
+  if (small) {
     taylor_sincos(dx[3], &sa, &ca);
     taylor_sincos(dx[4], &sb, &cb);
     taylor_sincos(dx[5], &sc, &cc);
@@ -1091,15 +1105,101 @@ __device__ __forceinline__ void finish_round_pose(const PicpArgs& A, const float
   if (j >= A.max_rounds) o.done = 1;
 }
 
+// ---- the finish with the pose update spread over the lanes of the finishing wave ----
+// Only word l of the new pose is needed in lane l (the publish and the control row are "lane l
+// owns word l"), so after the uniform solve and rotation lane l < 12 computes word l alone instead
+// of every lane computing all twelve.  With i = l % 3 and base = 3 (l / 3), words 0-8 being R
+// column-major and 9-11 t, word l is row i of Rd times old[base .. base+2], plus dx[i] for t:
+// one formula for both.  FinishLanes holds what depends on the lane only, made once per launch:
+// the row masks (all ones where l % 3 == i, l < 12), the t mask (9 <= l < 12) and the word-12
+// mask, as opaque VGPR values (as TotalLane: plain selects of the lane become compares whose lane
+// masks are hoisted into SGPR pairs and spilled), and the LDS word index of old[0].
+struct FinishLanes {
+  unsigned row[3], tmask, m12;
+  int base;
+};
+
+__device__ __forceinline__ FinishLanes finish_lanes(int lane) {
+  FinishLanes k;
+  const bool pose = lane < 12;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) k.row[i] = (pose && lane % 3 == i) ? ~0u : 0u;
+  k.tmask = (lane >= 9 && lane < 12) ? ~0u : 0u;
+  k.m12 = (lane == 12) ? ~0u : 0u;
+  k.base = pose ? 3 * (lane / 3) : 0;
+  asm volatile("" : "+v"(k.row[0]), "+v"(k.row[1]), "+v"(k.row[2]), "+v"(k.tmask), "+v"(k.m12), "+v"(k.base));
+  return k;
+}
+
+__device__ __forceinline__ float lanes_pick(const FinishLanes& k, float a0, float a1, float a2) {
+  return __uint_as_float((__float_as_uint(a0) & k.row[0]) | (__float_as_uint(a1) & k.row[1]) |
+                         (__float_as_uint(a2) & k.row[2]));
+}
+
+// finish_round_pose for a whole wave: the same RoundOut and chi_prev in every lane, and the
+// return value is word l of the new pose in lane l < 12 (unspecified in the other lanes).  pose:
+// the twelve words of the old pose (LDS or global), read per lane before the solve.  The
+// convergence quotient (an IEEE division that feeds only the done word) is computed ahead of the
+// solve, unconditionally: prev <= 1e-10 selects 0 whatever the quotient is, so the same bits as
+// the branch of finish_round_pose.
+// The three products of a word are summed as apply_update's are where the pose is live in
+// registers (the round kernel, the persistent kernel with one item per lane), a contraction that
+// was the compiler's choice and is not the same for every row of Rd: rows 1 and 2 are
+// fma(Rdi2, o2, fma(Rdi0, o0, Rdi1 * o1)), and row 0, whose Rd01 is a negated product, is
+// fma(Rd02, o2, fma(Rd01, o1, Rd00 * o0)); t adds dx separately.  Here it is written out (fp
+// contract off) and no longer rests on the compiler: each lane multiplies its "first" pair, then
+// fuses the "second" and the third.  (Where the pose is re-read from LDS, the persistent kernel
+// with two or more items per lane, the compiler sums row 0 as the other rows; those kernels keep
+// the uniform form and their bits.)  t's add is selected, not masked to an add of zero, which
+// would turn a -0 word of R into +0.
+__device__ __forceinline__ float finish_round_lanes(const PicpArgs& A, const float* tw, const float* pose, int j,
+                                                    const FinishLanes& k, float& chi_prev, RoundOut& o) {
+#pragma clang fp contract(off)
+  const float old0 = pose[k.base], old1 = pose[k.base + 1], old2 = pose[k.base + 2];
+  o.chi_in = tw[PICP_P_CHI_IN];
+  o.chi_out = tw[PICP_P_CHI_OUT];
+  o.n_in = __float_as_int(tw[PICP_P_N_IN]);
+  o.n_proj = __float_as_int(tw[PICP_P_N_PROJ]);
+  o.converged = 0;
+  if (o.n_in < A.min_inliers) {  // the pose stays: lane l's own old word
+    o.ok = 0;
+    o.done = 1;
+    return lanes_pick(k, old0, old1, old2);
+  }
+  // exec/icp_test.cpp:99-106, the quotient first
+  const float prev = chi_prev, cur = o.chi_in;
+  float quot = fabsf(prev - cur) / prev;
+  asm volatile("" : "+v"(quot));  // computed here, not sunk under a branch behind the solve
+  const float rel = (prev > 1e-10f) ? quot : 0.0f;
+  const bool conv = rel < A.conv_eps;
+  float dx[6];
+  ldl6_solve(tw, dx);
+  float Rd[3][3];
+  update_rotation<true>(dx, Rd);
+  // rows 1, 2: (Rdi1, old1) first, (Rdi0, old0) second; row 0 the other way round
+  const unsigned u0 = __float_as_uint(old0), u1 = __float_as_uint(old1), r0 = k.row[0];
+  const float of = __uint_as_float((u0 & r0) | (u1 & ~r0)), os = __uint_as_float((u1 & r0) | (u0 & ~r0));
+  float s = lanes_pick(k, Rd[0][0], Rd[1][1], Rd[2][1]) * of;
+  s = fmaf(lanes_pick(k, Rd[0][1], Rd[1][0], Rd[2][0]), os, s);
+  s = fmaf(lanes_pick(k, Rd[0][2], Rd[1][2], Rd[2][2]), old2, s);
+  // t: dx + s with dx as the first operand, as the uniform form compiles: where both are NaN the
+  // add returns the first one's sign, and the compiler commutes a plain + (inline assembly: the
+  // operand order is part of the result here)
+  float st;
+  asm("v_add_f32_e32 %0, %1, %2" : "=v"(st) : "v"(lanes_pick(k, dx[0], dx[1], dx[2])), "v"(s));
+  const float w = __uint_as_float((__float_as_uint(st) & k.tmask) | (__float_as_uint(s) & ~k.tmask));
+  o.ok = 1;
+  o.converged = conv ? 1 : 0;
+  o.done = (conv || j >= A.max_rounds) ? 1 : 0;
+  chi_prev = conv ? prev : cur;
+  return w;
+}
+
 // The 128-byte state after round j, written field by field (padding zeroed): a whole-struct copy
 // from a local goes through a scratch alloca (SROA cannot split the memcpy).  dst: LDS or global.
+// store_state_rest: everything but the pose (finish_round_lanes has the pose one word per lane).
 template <typename S>
-__device__ __forceinline__ void store_state(S* dst, const float R[9], const float t[3], float chi_prev,
-                                            const RoundOut& o, int j) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) dst->R[i] = R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) dst->t[i] = t[i];
+__device__ __forceinline__ void store_state_rest(S* dst, float chi_prev, const RoundOut& o, int j) {
   dst->chi_prev = chi_prev;
   dst->chi_in = o.chi_in;
   dst->chi_out = o.chi_out;
@@ -1111,6 +1211,16 @@ __device__ __forceinline__ void store_state(S* dst, const float R[9], const floa
   dst->converged = o.converged;
 #pragma unroll
   for (int i = 0; i < 11; ++i) dst->pad[i] = 0;
+}
+
+template <typename S>
+__device__ __forceinline__ void store_state(S* dst, const float R[9], const float t[3], float chi_prev,
+                                            const RoundOut& o, int j) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) dst->R[i] = R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) dst->t[i] = t[i];
+  store_state_rest(dst, chi_prev, o, j);
 }
 
 // finish_round_pose on a stored state (the multi-launch round kernel: one lane).

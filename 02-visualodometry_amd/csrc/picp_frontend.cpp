@@ -273,3 +273,28 @@ extern "C" int picp_selftest_rcp(int device, int e_lo, int e_hi, uint64_t* misma
   *mismatches = h;
   return PICP_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// self-test: the lane-parallel finish of a round against the uniform one (picp_device.h)
+// ------------------------------------------------------------------------------------
+extern "C" int picp_selftest_finish(int device, int64_t n_cases, const uint32_t* cases, uint64_t* mismatches,
+                                    uint32_t* out) {
+  CHECK_ARG(mismatches && cases && n_cases > 0 && n_cases <= (1 << 24), "picp_selftest_finish: bad argument");
+  HIP_TRY(hipSetDevice(device));
+  const size_t b_in = (size_t)n_cases * PICP_SELFTEST_FINISH_IN * 4, b_out = (size_t)n_cases * 2 * PICP_SELFTEST_FINISH_OUT * 4;
+  const size_t o_out = (b_in + 255) & ~(size_t)255, o_bad = o_out + ((b_out + 255) & ~(size_t)255);
+  char* buf = nullptr;
+  HIP_TRY(hipMalloc(&buf, o_bad + sizeof(unsigned long long)));
+  hipError_t e = hipMemcpy(buf, cases, b_in, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(buf + o_out, 0, o_bad + sizeof(unsigned long long) - o_out);
+  if (e == hipSuccess)
+    e = picp_launch_finish_check(nullptr, n_cases, (const unsigned*)buf, (unsigned long long*)(buf + o_bad),
+                                 (unsigned*)(buf + o_out));
+  unsigned long long h = 0;
+  if (e == hipSuccess) e = hipMemcpy(&h, buf + o_bad, sizeof(h), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out) e = hipMemcpy(out, buf + o_out, b_out, hipMemcpyDeviceToHost);
+  hipFree(buf);
+  if (e != hipSuccess) return set_err(PICP_ERR_DEVICE, "picp_selftest_finish: %s", hipGetErrorString(e));
+  *mismatches = h;
+  return PICP_OK;
+}

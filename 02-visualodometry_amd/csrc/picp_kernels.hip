@@ -425,3 +425,81 @@ extern "C" hipError_t picp_launch_rcp_check(hipStream_t stream, int e_lo, int e_
   hipLaunchKernelGGL(picp_rcp_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, e_lo, e_hi, bad);
   return hipGetLastError();
 }
+
+// --------------------- self-test of the lane-parallel finish ---------------------------
+// One wave per case runs the uniform finish (finish_round_pose, what the round kernel above runs)
+// and the lane-parallel one (finish_round_lanes, the persistent kernel's) on the same totals, pose
+// and loop state, and counts into *bad the output words that differ in any bit: the twelve pose
+// words, done, ok, converged, chi_prev, chi_in, chi_out, n_in, n_proj.  A case is
+// PICP_SELFTEST_FINISH_IN words (include/picp_c.h); out (may be null) gets, per case, the
+// PICP_SELFTEST_FINISH_OUT words of the lane-parallel form and then those of the uniform one.
+#define PICP_FCHK_WAVES 4
+extern "C" __global__ __launch_bounds__(64 * PICP_FCHK_WAVES) void picp_finish_check_kernel(
+    int64_t n, const unsigned* __restrict__ cases, unsigned long long* bad, unsigned* __restrict__ out) {
+  __shared__ float s_tw[PICP_FCHK_WAVES][PICP_NPART];
+  __shared__ float s_old[PICP_FCHK_WAVES][12];
+  __shared__ unsigned s_ref[PICP_FCHK_WAVES][PICP_SELFTEST_FINISH_OUT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * PICP_FCHK_WAVES + wave;
+  if (i >= n) return;  // a whole wave: only wave barriers below
+  const unsigned* c = cases + i * PICP_SELFTEST_FINISH_IN;
+  if (lane < PICP_NPART) s_tw[wave][lane] = __uint_as_float(c[lane]);
+  if (lane < 12) s_old[wave][lane] = __uint_as_float(c[PICP_NPART + lane]);
+  PicpArgs A = {};
+  const float chi_prev0 = __uint_as_float(c[44]);
+  A.conv_eps = __uint_as_float(c[45]);
+  A.min_inliers = (int32_t)c[46];
+  A.max_rounds = (int32_t)c[47];
+  const int j = (int)c[48];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  // the uniform form: every lane the same values
+  float R[9], t[3], chi_a = chi_prev0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = s_old[wave][k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = s_old[wave][9 + k];
+  RoundOut oa;
+  finish_round_pose(A, s_tw[wave], j, R, t, chi_a, oa);
+  // the lane-parallel form: lane l < 12 gets word l
+  float chi_b = chi_prev0;
+  RoundOut ob;
+  const FinishLanes fl = finish_lanes(lane);
+  const float w = finish_round_lanes(A, s_tw[wave], s_old[wave], j, fl, chi_b, ob);
+  if (lane == 0) {
+    unsigned* r = s_ref[wave];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r[k] = __float_as_uint(R[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[9 + k] = __float_as_uint(t[k]);
+    r[12] = (unsigned)oa.done; r[13] = (unsigned)oa.ok; r[14] = (unsigned)oa.converged;
+    r[15] = __float_as_uint(chi_a); r[16] = __float_as_uint(oa.chi_in); r[17] = __float_as_uint(oa.chi_out);
+    r[18] = (unsigned)oa.n_in; r[19] = (unsigned)oa.n_proj;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < PICP_SELFTEST_FINISH_OUT) {
+    unsigned mine = __float_as_uint(w);  // lanes 0-11; the rest is uniform, lane l takes word l
+    const unsigned rest[8] = {(unsigned)ob.done, (unsigned)ob.ok, (unsigned)ob.converged, __float_as_uint(chi_b),
+                              __float_as_uint(ob.chi_in), __float_as_uint(ob.chi_out), (unsigned)ob.n_in,
+                              (unsigned)ob.n_proj};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mine = (lane == 12 + k) ? rest[k] : mine;
+    if (mine != s_ref[wave][lane]) atomicAdd(bad, 1ull);
+    if (out) {
+      out[i * (2 * PICP_SELFTEST_FINISH_OUT) + lane] = mine;
+      out[i * (2 * PICP_SELFTEST_FINISH_OUT) + PICP_SELFTEST_FINISH_OUT + lane] = s_ref[wave][lane];
+    }
+  }
+}
+
+extern "C" hipError_t picp_launch_finish_check(hipStream_t stream, int64_t n, const unsigned* cases,
+                                               unsigned long long* bad, unsigned* out) {
+  if (n <= 0) return hipSuccess;
+  const int64_t grid = (n + PICP_FCHK_WAVES - 1) / PICP_FCHK_WAVES;
+  hipLaunchKernelGGL(picp_finish_check_kernel, dim3((unsigned)grid), dim3(64 * PICP_FCHK_WAVES), 0, stream, n, cases,
+                     bad, out);
+  return hipGetLastError();
+}

@@ -23,6 +23,11 @@ hipError_t picp_launch_triangulate(hipStream_t stream, const float* P1, const fl
                                    const float2* uv2, int64_t q, float* xyz);
 // counts into *bad the floats of binades [e_lo, e_hi), both signs, whose rcp_rn differs from 1.0f / x
 hipError_t picp_launch_rcp_check(hipStream_t stream, int e_lo, int e_hi, unsigned long long* bad);
+// finish_round_pose against finish_round_lanes on n cases (device pointers; the layout of a case and
+// of out -- both forms' words, may be null --: picp_c.h picp_selftest_finish); counts the differing
+// words into *bad
+hipError_t picp_launch_finish_check(hipStream_t stream, int64_t n, const unsigned* cases,
+                                    unsigned long long* bad, unsigned* out);
 
 // ---- picp_persistent.hip
 hipError_t picp_launch_persistent(hipStream_t stream, int grid, int npt, const float* X, const float* Y,

@@ -44,6 +44,15 @@ typedef __attribute__((address_space(1))) unsigned int gu32_t;
 // 11), so the source and that schedule stay.
 #define PICP_SWEEP_STAGGER 8
 #define PICP_SWEEP_MIN_NPT 2  // the staggered sweep from this many items per lane on
+// The first sweep pass of every solver wave is issued this long after the block's post-linearize
+// barrier (the kernel's sweep_lag; PICP_SWEEP_LAG_NS overrides it) where the sweep is not staggered
+// and the problem has follower blocks.  The followers start a round one pose hand-off after their
+// solver, so the last of them publishes about 0.6 us after the solver's barrier; the measured
+// curve on the 100k frame (profiles/r13/round/ab_lag_curve.log) has its best at 600 ns, within
+// 1 % of it from 550 to 650 and above no lag from 450 to 700.  With two staggered passes in flight
+// (PICP_SWEEP_MIN_NPT items per lane and more) no lag from 0 to 600 ns moved C3 and longer ones
+// lost, and the lag's code in those kernels cost C3 2 %, so they are compiled without it.
+#define PICP_SWEEP_LAG_NS_DEFAULT 600
 #define PICP_POSE_GRAN 16   // pose granules per set: R(9) t(3) done(1) solver XCC id(1) pad(2)
 // Solver blocks per problem.  Blocks kb and kb + 8j share an XCD under round-robin placement, so solver
 // kb & 7 publishes where its followers' polls are L2 hits instead of fabric round trips: an
@@ -78,17 +87,36 @@ __device__ unsigned long long picp_pstamps[2][256][8];
 // double sums (7), the stretch that holds the wait for a sweep pass still in flight.
 #define PSTAMP_W1(k) PSTAMP_T(k, 64)
 extern "C" hipError_t picp_debug_pstamps(unsigned long long* out, size_t n_words);
-// the leader's sweep, thread 0 (wave 0): each pass's issue and return times, rounds 11 and 12
-__device__ unsigned long long picp_sweepstamps[2][64];
+// the leader's sweep, per wave (its first lane still in the sweep, so the passes are the wave's and
+// not one lane's): each pass's issue (slot 2k) and return (2k + 1) times, the post-linearize
+// barrier (62) and the pass count (63), rounds 11 and 12
+#define PICP_SWS_BAR 62
+#define PICP_SWS_COUNT 63
+__device__ unsigned long long picp_sweepstamps[2][PICP_PBLOCK / 64][64];
+#define SWSTAMP_V(k, val)                                                                      \
+  do {                                                                                         \
+    const int k_ = (k); /* once: the sweep passes a counter's post-increment */                \
+    if (blockIdx.x == 0 && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1 &&   \
+        (epoch == 11 || epoch == 12) && k_ < 64)                                               \
+      picp_sweepstamps[epoch - 11][threadIdx.x >> 6][k_] = (val);                               \
+  } while (0)
 #define SWSTAMP(k)                                                                             \
   do {                                                                                         \
-    if (threadIdx.x == 0 && (epoch == 11 || epoch == 12) && (k) < 64)                          \
-      picp_sweepstamps[epoch - 11][(k)] = __builtin_amdgcn_s_memrealtime();                     \
+    const int kp_ = (k);                                                                       \
+    if (kp_ < PICP_SWS_BAR) SWSTAMP_V(kp_, __builtin_amdgcn_s_memrealtime());                   \
   } while (0)
+#define SWSTAMP_BAR() SWSTAMP_V(PICP_SWS_BAR, __builtin_amdgcn_s_memrealtime())
+#define SWSTAMP_COUNT(n) SWSTAMP_V(PICP_SWS_COUNT, (unsigned long long)(n))
 extern "C" hipError_t picp_debug_sweepstamps(unsigned long long* out, size_t n_words);
 #else
 #define SWSTAMP(k) \
   do {             \
+  } while (0)
+#define SWSTAMP_BAR() \
+  do {                \
+  } while (0)
+#define SWSTAMP_COUNT(n) \
+  do {                   \
   } while (0)
 #define PSTAMP(k) \
   do {            \
@@ -133,13 +161,11 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     const float* __restrict__ U, const float* __restrict__ V, const PicpArgs A,
     const PicpState* __restrict__ st_in, PicpState* __restrict__ st_out,
     unsigned long long* gpart, unsigned long long* gpose, unsigned int* err, unsigned int* tagbase,
-    unsigned long long* unused_slot, unsigned long long timeout_ticks) {
-  // unused_slot (always null): the kernel-argument slot of the deleted arrival counter.  Dropping
-  // it moves timeout_ticks' kernarg offset and with it the NPT = 8 schedule (about 380 of 4,400
-  // instructions reordered, same registers); the C2/C3 A/B of that build had one C3 median 0.06 %
-  // under the parent's band (profiles/r07/prune/ab.log), so the slot stays and the code is the
-  // measured one.
-  (void)unused_slot;
+    unsigned long long sweep_lag, unsigned long long timeout_ticks) {
+  // sweep_lag (s_memrealtime ticks, 10 ns): the solvers' first sweep pass is issued this long after
+  // the block's post-linearize barrier (below).  It has the kernel-argument slot of the deleted
+  // arrival counter, so timeout_ticks keeps its kernarg offset (moving it reordered the NPT = 8
+  // schedule, profiles/r07/prune/ab.log).
   __shared__ double s_red[PICP_NPART][BS / 64];  // term-major: one row per combining lane
   __shared__ float s_tot[PICP_NPART];
   __shared__ float s_wave[BS / 64][PICP_NPART];
@@ -225,6 +251,20 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   const float inv_thr = 1.0f / thr;
   const bool keep = A.keep_outliers != 0;
   const TotalLane tl = total_lane(A, lane);  // the finishing wave: lane e converts total e
+  // The finish by lanes (below) with one item per lane, where the linearize leaves registers to
+  // spare: its per-lane constants and the word of pose granule 13 (this solver's XCC id) are made
+  // once and stay in VGPRs.  With more items per lane the kernels keep the uniform finish: their
+  // registers are bound (the constants live through the linearize spilled; read from LDS each
+  // round the finish by lanes measured C3 inside the uniform one's band, profiles/r13/round/
+  // ab_leave_one_out.log), and as compiled they are instruction for instruction what they were.
+  constexpr bool LANES = (NPT == 1);
+  FinishLanes fl = {};
+  unsigned xcc_word = 0u;
+  if constexpr (LANES) {
+    fl = finish_lanes(lane);
+    xcc_word = lane == 13 ? my_xcc : 0u;
+    asm volatile("" : "+v"(xcc_word));
+  }
 
   // The slice has landed before the first round: the round loop's waits then count nothing that
   // was issued before it, so a follower's poll left in flight (below) is never waited for by the
@@ -281,6 +321,18 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     const float wsum = wave_counts(wave_reduce32(v, lane), lane, nc);
     if ((lane & 1) == 0) s_wave[wave][lane >> 1] = wsum;
     __syncthreads();
+    // A solver's first sweep pass is a round trip of 0.6-1.1 us, and whatever it misses costs a
+    // second one.  Issued straight after this barrier (waves 1-7 have no publish to do) it leaves
+    // before the later followers have published, so every solver wave issues it at one time
+    // point instead, sweep_lag after the barrier: wave 0 waits only what is left after its
+    // publish.  Only tags are trusted, so the lag is never a matter of correctness: a lag too short
+    // costs the second pass it was meant to save, one too long its own length.
+    constexpr bool TIMED = (NPT < PICP_SWEEP_MIN_NPT);
+    unsigned long long sweep_at = 0;
+    if constexpr (TIMED) {
+      if (solver && sweep_lag) sweep_at = __builtin_amdgcn_s_memrealtime() + sweep_lag;
+    }
+    if (solver) SWSTAMP_BAR();
     if (tid < PICP_NPART) {
       float sum = s_wave[0][tid];
 #pragma unroll
@@ -309,6 +361,12 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
         if (g + NG * i < nblk) pending |= 1u << i;
       }
       [[maybe_unused]] int npass = 0;  // sweep passes (diagnostic stamps)
+      if constexpr (TIMED) {
+        if (sweep_lag) {  // never past the round's deadline
+          const unsigned long long until = sweep_at < deadline ? sweep_at : deadline;
+          while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(1);
+        }
+      }
       constexpr int SWEEP_ST = (NPT >= PICP_SWEEP_MIN_NPT) ? PICP_SWEEP_STAGGER : 0;
       if constexpr (SWEEP_ST > 0) {
         u32x4 ga[MAXG], gb[MAXG];
@@ -327,19 +385,26 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
               pending &= ~(1u << i);
             }
         };
+        [[maybe_unused]] int nissue = 0;  // passes issued / taken (diagnostic stamps)
         unsigned wa = pending, wb;
+        SWSTAMP(2 * nissue++);
         issue(ga, wa);
         __builtin_amdgcn_s_sleep(SWEEP_ST);
         wb = pending;
+        SWSTAMP(2 * nissue++);
         issue(gb, wb);
         for (;;) {
           take(ga, wa);
+          SWSTAMP(2 * npass++ + 1);
           if (!pending) break;
           wa = pending;
+          SWSTAMP(2 * nissue++);
           issue(ga, wa);
           take(gb, wb);
+          SWSTAMP(2 * npass++ + 1);
           if (!pending) break;
           wb = pending;
+          SWSTAMP(2 * nissue++);
           issue(gb, wb);
           if (timed_out(deadline)) {
             __hip_atomic_store(errw, 1u, RLX_AGENT);
@@ -369,6 +434,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
           }
         }
       }
+      SWSTAMP_COUNT(npass);
       // every gv[i]: a block's granule pair, or the zeros it started with where g + NG*i is past
       // the problem's blocks (never loaded).  Adding those zeros is exact and the sum cannot be
       // -0 (it starts at +0), so no guard per i: the same bits, i ascending
@@ -397,65 +463,109 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       //      lanes 0-15 each publish their pose word directly; the other waves meet wave 0 at
       //      the barrier below, off the publish path ----
       if (wave == 0) {
-        // the pose: kept from the round start when the linearize leaves registers to spare (one
-        // item per lane), else re-read here (three 16-B LDS loads, landing during the combine):
-        // kept live through a register-bound linearize it spilled; s_pose changes only after the
-        // finish
-        float pr[9], pt[3];
-        if constexpr (NPT == 1) {
-          pr[0] = T.r00; pr[1] = T.r10; pr[2] = T.r20; pr[3] = T.r01; pr[4] = T.r11; pr[5] = T.r21;
-          pr[6] = T.r02; pr[7] = T.r12; pr[8] = T.r22; pt[0] = T.t0; pt[1] = T.t1; pt[2] = T.t2;
-        } else {
+        if constexpr (LANES) {
+          if (lane < PICP_NPART) {
+            double ws[BS / 64];  // every load issued before the first add
 #pragma unroll
-          for (int i = 0; i < 9; ++i) pr[i] = s_pose[i];
+            for (int w = 0; w < BS / 64; ++w) ws[w] = s_red[lane][w];
+            double t = ws[0];
 #pragma unroll
-          for (int i = 0; i < 3; ++i) pt[i] = s_pose[9 + i];
-        }
-        if (lane < PICP_NPART) {
-          double ws[BS / 64];  // every load issued before the first add
-#pragma unroll
-          for (int w = 0; w < BS / 64; ++w) ws[w] = s_red[lane][w];
-          double t = ws[0];
-#pragma unroll
-          for (int w = 1; w < BS / 64; ++w) t += ws[w];
-          s_tot[lane] = total_word(tl, t);  // lane e converts total e
-        }
-        __builtin_amdgcn_wave_barrier();
-        {
-          // the wave finishes the round (every lane the same values, loop state in registers)
-          RoundOut o;
-          PSTAMP(4);
-          finish_round_pose(A, s_tot, (int)epoch, pr, pt, chi_prev, o);
-          PSTAMP(5);
-          // (read here, after the solve: hoisted to the combine's loads it measured no faster,
-          // DESIGN.md Appendix A "s_tmo read early")
-          if (s_tmo) o.done = 1;  // a sweep timed out
-          // ---- publish the new pose (and the done flag): lane l < 16 owns word l ----
-          unsigned pw[PICP_POSE_GRAN];
-#pragma unroll
-          for (int i = 0; i < 9; ++i) pw[i] = __float_as_uint(pr[i]);
-#pragma unroll
-          for (int i = 0; i < 3; ++i) pw[9 + i] = __float_as_uint(pt[i]);
-          pw[12] = (unsigned)o.done;
-          pw[13] = my_xcc;
-          pw[14] = pw[15] = 0u;
-          const float w = __uint_as_float(lane_word16(pw, lane));
-          if (lane < PICP_POSE_GRAN) {
-            const unsigned long long gw = granule(tbase + epoch, w);
-            __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
+            for (int w = 1; w < BS / 64; ++w) t += ws[w];
+            s_tot[lane] = total_word(tl, t);  // lane e converts total e
           }
-          if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) s_pose[i] = pr[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) s_pose[9 + i] = pt[i];
-            s_done = o.done;
+          __builtin_amdgcn_wave_barrier();
+          {
+            // the wave finishes the round: the solve and the rotation in every lane, then lane
+            // l < 12 computes word l of the new pose from its three words of s_pose (read per lane
+            // ahead of the solve; s_pose changes only below); chi_prev stays in registers
+            RoundOut o;
+            PSTAMP(4);
+            const float w = finish_round_lanes(A, s_tot, s_pose, (int)epoch, fl, chi_prev, o);
+            PSTAMP(5);
+            // (read here, after the solve: hoisted to the combine's loads it measured no faster,
+            // DESIGN.md Appendix A "s_tmo read early")
+            if (s_tmo) o.done = 1;  // a sweep timed out
+            // ---- publish the new pose (and the done flag): lane l < 16 owns word l -- the pose
+            //      (0-11), done (12), this solver's XCC id (13), zero (14, 15) ----
+            const unsigned cw = (__float_as_uint(w) & (fl.row[0] | fl.row[1] | fl.row[2])) |
+                                ((unsigned)o.done & fl.m12) | xcc_word;
+            if (lane < PICP_POSE_GRAN) {
+              const unsigned long long gw = ((unsigned long long)(tbase + epoch) << 32) | cw;
+              __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
+            }
+            if (lane < 13) s_ctl[lane] = cw;  // the pose and s_done (word 13, s_l2, is the follower's)
             if (o.done && leader) {
-              store_state(st_out + p, pr, pt, chi_prev, o, (int)epoch);
-              // every block of the problem read tbase before publishing round 1, and this is
-              // after its last round: the next launch's tags start past this one's
-              __hip_atomic_store(tbase_p, tbase + epoch, RLX_AGENT);
+              if (lane < 12) ((unsigned*)(st_out + p))[lane] = cw;  // R (9), t (3): lane l owns word l
+              if (lane == 0) {
+                store_state_rest(st_out + p, chi_prev, o, (int)epoch);
+                // every block of the problem read tbase before publishing round 1, and this is
+                // after its last round: the next launch's tags start past this one's
+                __hip_atomic_store(tbase_p, tbase + epoch, RLX_AGENT);
+              }
+            }
+          }
+        } else {
+          // the pose: kept from the round start when the linearize leaves registers to spare (one
+          // item per lane), else re-read here (three 16-B LDS loads, landing during the combine):
+          // kept live through a register-bound linearize it spilled; s_pose changes only after the
+          // finish
+          float pr[9], pt[3];
+          if constexpr (NPT == 1) {
+            pr[0] = T.r00; pr[1] = T.r10; pr[2] = T.r20; pr[3] = T.r01; pr[4] = T.r11; pr[5] = T.r21;
+            pr[6] = T.r02; pr[7] = T.r12; pr[8] = T.r22; pt[0] = T.t0; pt[1] = T.t1; pt[2] = T.t2;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) pr[i] = s_pose[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) pt[i] = s_pose[9 + i];
+          }
+          if (lane < PICP_NPART) {
+            double ws[BS / 64];  // every load issued before the first add
+#pragma unroll
+            for (int w = 0; w < BS / 64; ++w) ws[w] = s_red[lane][w];
+            double t = ws[0];
+#pragma unroll
+            for (int w = 1; w < BS / 64; ++w) t += ws[w];
+            s_tot[lane] = total_word(tl, t);  // lane e converts total e
+          }
+          __builtin_amdgcn_wave_barrier();
+          {
+            // the wave finishes the round (every lane the same values, loop state in registers)
+            RoundOut o;
+            PSTAMP(4);
+            finish_round_pose(A, s_tot, (int)epoch, pr, pt, chi_prev, o);
+            PSTAMP(5);
+            // (read here, after the solve: hoisted to the combine's loads it measured no faster,
+            // DESIGN.md Appendix A "s_tmo read early")
+            if (s_tmo) o.done = 1;  // a sweep timed out
+            // ---- publish the new pose (and the done flag): lane l < 16 owns word l ----
+            unsigned pw[PICP_POSE_GRAN];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) pw[i] = __float_as_uint(pr[i]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) pw[9 + i] = __float_as_uint(pt[i]);
+            pw[12] = (unsigned)o.done;
+            pw[13] = my_xcc;
+            pw[14] = pw[15] = 0u;
+            const float w = __uint_as_float(lane_word16(pw, lane));
+            if (lane < PICP_POSE_GRAN) {
+              const unsigned long long gw = granule(tbase + epoch, w);
+              __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
+            }
+            if (lane == 0) {
+#pragma unroll
+              for (int i = 0; i < 9; ++i) s_pose[i] = pr[i];
+#pragma unroll
+              for (int i = 0; i < 3; ++i) s_pose[9 + i] = pt[i];
+              s_done = o.done;
+              if (o.done && leader) {
+                store_state(st_out + p, pr, pt, chi_prev, o, (int)epoch);
+                // every block of the problem read tbase before publishing round 1, and this is
+                // after its last round: the next launch's tags start past this one's
+                __hip_atomic_store(tbase_p, tbase + epoch, RLX_AGENT);
+              }
             }
           }
         }
@@ -528,7 +638,7 @@ extern "C" hipError_t picp_debug_sweepstamps(unsigned long long* out, size_t n_w
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(picp_sweepstamps), (n_words < cap ? n_words : cap) * 8, 0,
                                      hipMemcpyDeviceToHost);
   if (e == hipSuccess) {  // clear for the next run (a shorter sweep leaves no stale passes)
-    static const unsigned long long zero[2 * 64] = {};
+    static const unsigned long long zero[sizeof(picp_sweepstamps) / sizeof(unsigned long long)] = {};
     e = hipMemcpyToSymbol(HIP_SYMBOL(picp_sweepstamps), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
   }
   return e;
@@ -579,11 +689,20 @@ extern "C" hipError_t picp_launch_persistent(hipStream_t stream, int grid, int n
                                              unsigned int* err, unsigned int* tagbase,
                                              unsigned long long timeout_ticks) {
   if (grid <= 0 || !args || !args->uniform || args->nblk_u > PICP_MAX_PBLK) return hipErrorInvalidValue;
+  // PICP_SWEEP_LAG_NS (read once; for tests and measurements): the lag of the solvers' first sweep
+  // pass, 0 = straight after the barrier, at most 100 us.  A problem whose blocks are all solvers
+  // has no follower to wait for: they publish as they leave the barrier, so no lag there.
+  static const unsigned long long sweep_lag = [] {
+    const char* e = getenv("PICP_SWEEP_LAG_NS");
+    long ns = e ? atol(e) : PICP_SWEEP_LAG_NS_DEFAULT;
+    ns = ns < 0 ? 0 : (ns > 100000 ? 100000 : ns);
+    return (unsigned long long)((ns + 5) / 10);  // s_memrealtime ticks
+  }();
   const int var = picp_variant(args->K, args->keep_outliers);
 #define PICP_LAUNCH_PV(N, PV)                                                                       \
   hipLaunchKernelGGL((picp_persistent_kernel<N, PV, PICP_PBLOCK>), dim3(grid), dim3(PICP_PBLOCK), 0, \
                      stream, X, Y, Z, U, V, *args, st_in, st_out, gpart, gpose, err, tagbase,         \
-                     (unsigned long long*)nullptr, timeout_ticks)
+                     args->nblk_u > PICP_PSOLVERS ? sweep_lag : 0ull, timeout_ticks)
 #define PICP_LAUNCH_P(N)                                                            \
   if (var == PICP_V_PINHOLE) PICP_LAUNCH_PV(N, PICP_V_PINHOLE);                     \
   else if (var == PICP_V_PINHOLE_KEEP) PICP_LAUNCH_PV(N, PICP_V_PINHOLE_KEEP);      \

@@ -44,7 +44,7 @@ EXPORTED = [
     "picp_triangulate", "picp_projection_matrix", "picp_match", "picp_match_batch", "picp_match_batch_form",
     "picp_vo_create", "picp_vo_destroy", "picp_vo_set_segments", "picp_vo_run", "picp_vo_run_async", "picp_vo_debug_matches", "picp_vo_debug_guard",
     "picp_vo_sync", "picp_vo_get_poses", "picp_vo_get_steps", "picp_vo_get_map", "picp_vo_time",
-    "picp_vo_info", "picp_selftest_rcp", "picp_essential_params_default", "picp_essential_batch",
+    "picp_vo_info", "picp_selftest_rcp", "picp_selftest_finish", "picp_essential_params_default", "picp_essential_batch",
     "picp_shard_range", "picp_shard_pad", "picp_shard_unpack", "picp_comm_unique_id", "picp_comm_create", "picp_comm_destroy", "picp_comm_info",
     "picp_comm_allreduce_max", "picp_comm_barrier", "picp_batch_allgather", "picp_batch_allgather_host",
     "picp_classify", "picp_batch_classify", "picp_batch_classify_time",
@@ -180,6 +180,7 @@ def lib():
         "picp_vo_get_map": ([vp, i, i64, fp, fp, ctypes.POINTER(i64)], i),
         "picp_vo_time": ([vp, i, fp], i),
         "picp_selftest_rcp": ([i, i, i, ctypes.POINTER(ctypes.c_uint64)], i),
+        "picp_selftest_finish": ([i, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p], i),
         "picp_vo_info": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i)], i),
         "picp_shard_range": ([i64, i, i, ctypes.POINTER(i64), ctypes.POINTER(i64)], i),
         "picp_shard_pad": ([i64, i], i64),
@@ -1081,3 +1082,20 @@ def selftest_rcp(e_lo=-8, e_hi=8, device=0):
     n = ctypes.c_uint64()
     _check(lib().picp_selftest_rcp(device, e_lo, e_hi, ctypes.byref(n)))
     return n.value
+
+
+SELFTEST_FINISH_IN, SELFTEST_FINISH_OUT = 52, 20  # include/picp_c.h
+
+
+def selftest_finish(cases, device=0):
+    """Runs the uniform and the lane-parallel finish of a round on every case (uint32 words,
+    shape (n, SELFTEST_FINISH_IN): include/picp_c.h picp_selftest_finish).  Returns (the count of
+    output words that differ between the two, the lane-parallel form's outputs and the uniform
+    form's, each uint32 (n, SELFTEST_FINISH_OUT))."""
+    cases = np.ascontiguousarray(cases, np.uint32)
+    if cases.ndim != 2 or cases.shape[1] != SELFTEST_FINISH_IN:
+        raise ValueError("cases must be (n, %d) uint32 words" % SELFTEST_FINISH_IN)
+    out = np.zeros((cases.shape[0], 2, SELFTEST_FINISH_OUT), np.uint32)
+    n = ctypes.c_uint64()
+    _check(lib().picp_selftest_finish(device, cases.shape[0], cases.ctypes.data, ctypes.byref(n), out.ctypes.data))
+    return n.value, out[:, 0].copy(), out[:, 1].copy()

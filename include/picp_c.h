@@ -566,6 +566,23 @@ int picp_vo_debug_guard(picp_vo_t* h, int64_t* bad_bytes, int* bad_buffer);
  * the mismatching floats of both signs with exponents in [e_lo, e_hi); expected 0. */
 int picp_selftest_rcp(int device, int e_lo, int e_hi, uint64_t* mismatches);
 
+/* The persistent kernel finishes a round with the pose update spread over the lanes of one wave
+ * (lane l computes word l of the new pose); the round kernel of the graph path computes the whole
+ * pose in every lane.  Both must give the same bits.  Runs both forms on n_cases inputs in one
+ * launch and counts the output words that differ; expected 0.
+ * A case is PICP_SELFTEST_FINISH_IN 32-bit words: 0-31 the round's converted totals (the 21
+ * entries of the upper triangle of H + damping I, row-major, as float; the 6 entries of -b;
+ * chi_in; chi_out; n_in and n_projected as int32; 0), 32-43 the pose (R column-major, t),
+ * 44 chi_prev, 45 conv_eps, 46 min_inliers (int32), 47 max_rounds (int32), 48 the round's
+ * number, counted from 1 (int32), 49-51 unused.
+ * out (may be NULL): 2 * PICP_SELFTEST_FINISH_OUT words per case, the words that are compared,
+ * first the lane-parallel form's and then the uniform form's: 0-11 the new pose, 12 done, 13 ok,
+ * 14 converged, 15 chi_prev, 16 chi_in, 17 chi_out, 18 n_in, 19 n_projected. */
+#define PICP_SELFTEST_FINISH_IN 52
+#define PICP_SELFTEST_FINISH_OUT 20
+int picp_selftest_finish(int device, int64_t n_cases, const uint32_t* cases, uint64_t* mismatches,
+                         uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

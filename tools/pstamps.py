@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Phase breakdown of the persistent kernel (diagnostic stamp build), rounds 11 and 12.
 Stamps: 0 round start, 1 partial published, 2 leader: sweep done / others: pose received,
-3 leader: solve done; the leader's sweep passes (issue, return) of thread 0; and what a round waits
+3 leader: solve done; the sweep passes (issue, return) of each of the leader's 8 waves (its first lane still sweeping),
+with the wave's post-linearize barrier and pass count; and what a round waits
 for besides its hand-offs (6, 7): in a follower, wave 1's round start and pose barrier beside the
 polling wave's (0, 2); in a solver, the sweep's exit and the end of the double sums."""
 import argparse
@@ -30,7 +31,7 @@ def main():
     b.set_poses(p["T_init"][None])
     L = picp_amd.lib()
     L.picp_debug_sweepstamps.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    sw = np.zeros((2, 64), np.uint64)
+    sw = np.zeros((2, 8, 64), np.uint64)  # round, wave, slot (picp_persistent.hip picp_sweepstamps)
     for _ in range(3):
         assert L.picp_debug_sweepstamps(sw.ctypes.data, sw.size) == 0  # read = clear
         b.solve(threshold=3000.0, max_rounds=50, conv_eps=-1.0)
@@ -69,16 +70,26 @@ def main():
             print("  followers pose barrier r11 -> published r12: median %d (min %d max %d)" % (
                 np.median(pub), pub.min(), pub.max()))
         last_pub = int(rel[:, 1].max())
-        # the leader's sweep passes (thread 0): issue -> loads returned, ns from the round start
-        p = sw[r].astype(np.int64)
-        n = int(np.count_nonzero(p)) // 2
-        passes = [((p[2 * i] - t0) * 10, (p[2 * i + 1] - t0) * 10) for i in range(n)]
-        print("  leader sweep passes (issue..return ns): %s" % "  ".join("%d..%d" % x for x in passes))
-        if passes:
-            dur = [b - a for a, b in passes]
-            after = [x for x in passes if x[0] >= last_pub]
-            print("  pass duration median %d ns (min %d max %d); %d passes, %d issued after the last publish (%d)" %
-                  (np.median(dur), min(dur), max(dur), n, len(after), last_pub))
+        # the leader's sweep passes of every wave: issue -> loads returned, ns from the round
+        # start (slot 62: the wave's post-linearize barrier, 63: its pass count)
+        first = []
+        for w in range(sw.shape[1]):
+            p = sw[r, w].astype(np.int64)
+            n = int(p[63])
+            passes = [((p[2 * i] - t0) * 10, (p[2 * i + 1] - t0) * 10) for i in range(min(n, 31)) if p[2 * i + 1]]
+            print("  leader wave %d: barrier %d, %d passes (issue..return ns): %s" % (
+                w, (p[62] - t0) * 10 if p[62] else -1, n, "  ".join("%d..%d" % x for x in passes)))
+            if passes:
+                first.append(passes[0][0])
+                dur = [b - a for a, b in passes]
+                after = [x for x in passes if x[0] >= last_pub]
+                print("    pass duration median %d ns (min %d max %d); %d issued after the last publish (%d)" %
+                      (np.median(dur), min(dur), max(dur), len(after), last_pub))
+        if first:
+            print("  first pass issued: wave 0 at %d, waves 1-7 at %s; spread %d ns" % (
+                first[0], " ".join(str(x) for x in first[1:]), max(first) - min(first)))
+            print("  last publish %d -> swept(all threads) %d: %d ns; swept -> pose stored (solve_end) %d ns" % (
+                last_pub, rel[0, 2], rel[0, 2] - last_pub, rel[0, 5] - rel[0, 2]))
     nxt = (buf[1, :nb, 0].astype(np.int64).min() - buf[0, :nb, 0].astype(np.int64).min()) * 10
     print("round period (first start r11 -> first start r12): %d ns" % nxt)
 
