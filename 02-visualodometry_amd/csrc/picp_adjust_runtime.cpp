@@ -57,12 +57,8 @@ void adjust_tracks_changed(picp_refine* h) {
 void adjust_free(picp_refine* h) {
   RefineAdjust& A = h->adj;
   drop_batch(h);
-  void* bufs[] = {A.T_d, A.cnt_d, A.pose_off_d, A.tmp_d, A.view_point_d, A.view_uv_d, A.movable_d,
-                  A.plane_off_d, A.pose_stats_d, A.sweeps_d, A.poses0_d, A.T0_d};
-  for (void* p : bufs)
-    if (p) hipFree(p);
   if (A.ev) hipEventDestroy(A.ev);
-  A = RefineAdjust{};
+  A = RefineAdjust{};  // the device buffers free themselves
 }
 
 extern "C" int picp_refine_set_fixed_poses(picp_refine_t* h, const uint8_t* fixed) {
@@ -121,11 +117,11 @@ static int view_build(picp_refine* h) {
   CHECK_ARG(h->n_points <= INT32_MAX, "adjust: more points than the view's int32 point index addresses");
   HIP_TRY(hipSetDevice(h->device));
   const int64_t no = h->n_obs;
-  int rc = grow((void**)&A.cnt_d, &A.cap_cnt, std::max(h->n_poses, 1), sizeof(int32_t));
-  if (!rc) rc = grow((void**)&A.pose_off_d, &A.cap_pose_off, (int64_t)h->n_poses + 1, sizeof(int64_t));
-  if (!rc) rc = grow((void**)&A.tmp_d, &A.cap_tmp, no, sizeof(int2));
-  if (!rc) rc = grow((void**)&A.view_point_d, &A.cap_view_point, no, sizeof(int32_t));
-  if (!rc) rc = grow((void**)&A.view_uv_d, &A.cap_view_uv, no, sizeof(float2));
+  int rc = A.cnt_d.grow(std::max(h->n_poses, 1));
+  if (!rc) rc = A.pose_off_d.grow((int64_t)h->n_poses + 1);
+  if (!rc) rc = A.tmp_d.grow(no);
+  if (!rc) rc = A.view_point_d.grow(no);
+  if (!rc) rc = A.view_uv_d.grow(no);
   if (rc) return rc;
   HIP_TRY(view_enqueue(h));
   A.pose_off.assign((size_t)h->n_poses + 1, 0);
@@ -160,8 +156,8 @@ static int batch_build(picp_refine* h) {
       A.batch = nullptr;
       return rc;
     }
-    rc = grow((void**)&A.movable_d, &A.cap_movable, np, sizeof(int32_t));
-    if (!rc) rc = grow((void**)&A.plane_off_d, &A.cap_plane_off, np, sizeof(int64_t));
+    rc = A.movable_d.grow(np);
+    if (!rc) rc = A.plane_off_d.grow(np);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(A.movable_d, A.movable.data(), (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(A.plane_off_d, A.batch->plane_off.data(), (size_t)np * sizeof(int64_t), hipMemcpyHostToDevice,
@@ -189,7 +185,7 @@ static int poses_prepare(picp_refine* h, const picp_params* prm, const char* who
   HIP_TRY(hipSetDevice(h->device));
   rc = view_build(h);
   if (!rc) rc = batch_build(h);
-  if (!rc) rc = grow((void**)&h->adj.pose_stats_d, &h->adj.cap_pose_stats, std::max(h->n_poses, 1), sizeof(picp_stats));
+  if (!rc) rc = h->adj.pose_stats_d.grow(std::max(h->n_poses, 1));
   return rc;
 }
 
@@ -278,7 +274,7 @@ static int adjust_prepare(picp_refine* h, const picp_adjust_params* prm, RefineA
   int rc = check_pose_params(&prm->poses);
   if (!rc) rc = refine_prepare(h, &prm->points, a);
   if (!rc && prm->sweeps > 0) rc = poses_prepare(h, &prm->poses, who);
-  if (!rc) rc = grow((void**)&h->adj.sweeps_d, &h->adj.cap_sweeps, std::max(prm->sweeps, 1), sizeof(picp_adjust_sweep));
+  if (!rc) rc = h->adj.sweeps_d.grow(std::max(prm->sweeps, 1));
   return rc;
 }
 
@@ -379,28 +375,23 @@ extern "C" int picp_refine_adjust_time(picp_refine_t* h, const picp_adjust_param
   }
   // the view again into the same buffers, reps times (the same entries in the same places)
   {
-    std::vector<EventPair> ev((size_t)reps);
-    for (auto& e : ev) HIP_TRY(e.create());
+    TimedSpans ev(reps);
+    HIP_TRY(ev.create());
     for (int r = 0; r < reps; ++r) {
-      HIP_TRY(hipEventRecord(ev[r].a, h->stream));
+      HIP_TRY(ev.begin(r, h->stream));
       HIP_TRY(view_enqueue(h));
-      HIP_TRY(hipEventRecord(ev[r].b, h->stream));
+      HIP_TRY(ev.end(r, h->stream));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream));
     double t = 0.0;
-    for (int r = 0; r < reps; ++r) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, ev[r].a, ev[r].b));
-      t += ms;
-    }
+    HIP_TRY(ev.sum_ms(h->stream, &t));
     *build_us = (float)(1000.0 * t / reps);
   }
   // what the call found, restored before every repetition outside the timed spans
   const size_t xb = (size_t)h->n_points * 3 * sizeof(float), pb = (size_t)h->n_poses * sizeof(RefinePose),
                tb = (size_t)h->n_poses * 16 * sizeof(float);
-  rc = grow((void**)&h->xyz0_d, &h->cap_xyz0, 3 * h->n_points, sizeof(float));
-  if (!rc) rc = grow((void**)&A.poses0_d, &A.cap_poses0, h->n_poses, sizeof(RefinePose));
-  if (!rc) rc = grow((void**)&A.T0_d, &A.cap_T0, 16 * (int64_t)h->n_poses, sizeof(float));
+  rc = h->xyz0_d.grow(3 * h->n_points);
+  if (!rc) rc = A.poses0_d.grow(h->n_poses);
+  if (!rc) rc = A.T0_d.grow(16 * (int64_t)h->n_poses);
   if (rc) return rc;
   if (xb) HIP_TRY(hipMemcpyAsync(h->xyz0_d, h->xyz_d, xb, hipMemcpyDeviceToDevice, h->stream));
   if (pb) HIP_TRY(hipMemcpyAsync(A.poses0_d, h->poses_d, pb, hipMemcpyDeviceToDevice, h->stream));
@@ -410,35 +401,23 @@ extern "C" int picp_refine_adjust_time(picp_refine_t* h, const picp_adjust_param
     if (xb) HIP_TRY(hipMemcpyAsync(h->xyz_d, h->xyz0_d, xb, hipMemcpyDeviceToDevice, h->stream));
     if (pb) HIP_TRY(hipMemcpyAsync(h->poses_d, A.poses0_d, pb, hipMemcpyDeviceToDevice, h->stream));
     if (tb) HIP_TRY(hipMemcpyAsync(A.T_d, A.T0_d, tb, hipMemcpyDeviceToDevice, h->stream));
-    std::vector<EventPair> ep((size_t)S), eg((size_t)S), es((size_t)S), ew((size_t)S);
-    for (int s = 0; s < S; ++s) {
-      HIP_TRY(ep[s].create());
-      HIP_TRY(eg[s].create());
-      HIP_TRY(es[s].create());
-      HIP_TRY(ew[s].create());
-    }
-    rc = adjust_sweeps(h, prm, &a, ep.data(), eg.data(), es.data(), ew.data());
+    TimedSpans ep(S), eg(S), es(S), ew(S);
+    HIP_TRY(ep.create());
+    HIP_TRY(eg.create());
+    HIP_TRY(es.create());
+    HIP_TRY(ew.create());
+    rc = adjust_sweeps(h, prm, &a, ep.ev.data(), eg.ev.data(), es.ev.data(), ew.ev.data());
     if (rc) return rc;
-    if (!A.batch) {
-      for (int s = 0; s < S; ++s) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ep[s].a, ep[s].b));
-        tx += ms;
-      }
-      continue;
-    }
-    HIP_TRY(hipStreamSynchronize(A.batch->stream));
-    for (int s = 0; s < S; ++s) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, ep[s].a, ep[s].b));
-      tx += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, eg[s].a, eg[s].b));
-      tg += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, ew[s].a, ew[s].b));
-      tg += ms;
-      HIP_TRY(hipEventElapsedTime(&ms, es[s].a, es[s].b));
-      tp += ms;
-    }
+    double t = 0.0;
+    HIP_TRY(ep.sum_ms(h->stream, &t));
+    tx += t;
+    if (!A.batch) continue;
+    HIP_TRY(eg.sum_ms(A.batch->stream, &t));
+    tg += t;
+    HIP_TRY(ew.sum_ms(A.batch->stream, &t));
+    tg += t;
+    HIP_TRY(es.sum_ms(A.batch->stream, &t));
+    tp += t;
   }
   const double per = 1000.0 / ((double)reps * S);
   *gather_us = (float)(tg * per);
@@ -451,8 +430,8 @@ int refine_load_device(picp_refine* h, int n_poses, const RefinePose* rposes, co
                        int64_t n_points, int64_t n_obs, const int64_t* track_off, const int32_t* obs_pose,
                        const float2* obs_uv, const float* xyz) {
   HIP_TRY(hipSetDevice(h->device));
-  int rc = grow((void**)&h->poses_d, &h->cap_poses, n_poses, sizeof(RefinePose));
-  if (!rc) rc = grow((void**)&h->adj.T_d, &h->adj.cap_T, 16 * (int64_t)n_poses, sizeof(float));
+  int rc = h->poses_d.grow(n_poses);
+  if (!rc) rc = h->adj.T_d.grow(16 * (int64_t)n_poses);
   if (rc) return rc;
   if (n_poses) {
     HIP_TRY(hipMemcpyAsync(h->poses_d, rposes, (size_t)n_poses * sizeof(RefinePose), hipMemcpyDeviceToDevice, h->stream));
@@ -467,9 +446,9 @@ int refine_load_device(picp_refine* h, int n_poses, const RefinePose* rposes, co
     h->adj.have_pose_stats = false;
   }
   if (tracks) {
-    rc = grow((void**)&h->off_d, &h->cap_off, n_points + 1, sizeof(int64_t));
-    if (!rc) rc = grow((void**)&h->obs_pose_d, &h->cap_obs_pose, n_obs, sizeof(int32_t));
-    if (!rc) rc = grow((void**)&h->obs_uv_d, &h->cap_obs_uv, n_obs, sizeof(float2));
+    rc = h->off_d.grow(n_points + 1);
+    if (!rc) rc = h->obs_pose_d.grow(n_obs);
+    if (!rc) rc = h->obs_uv_d.grow(n_obs);
     if (rc) {
       h->n_points = -1;
       return rc;
@@ -485,7 +464,7 @@ int refine_load_device(picp_refine* h, int n_poses, const RefinePose* rposes, co
     h->max_pose_idx = n_obs > 0 ? n_poses - 1 : -1;  // the caller's indices are in range by construction
     adjust_tracks_changed(h);
   }
-  rc = grow((void**)&h->xyz_d, &h->cap_xyz, 3 * h->n_points, sizeof(float));
+  rc = h->xyz_d.grow(3 * h->n_points);
   if (rc) return rc;
   if (h->n_points)
     HIP_TRY(hipMemcpyAsync(h->xyz_d, xyz, (size_t)h->n_points * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));

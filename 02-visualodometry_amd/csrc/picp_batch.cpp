@@ -375,14 +375,9 @@ extern "C" int picp_batch_destroy(picp_batch_t* b) {
   for (int k = 0; k < 2; ++k) renew(&b->st_d[k], 0);
   renew(&b->sync_d, 0);
   if (b->st_pinned) hipHostFree(b->st_pinned);
-  {
-    void* cls[] = {b->cls.tables, b->cls.scan, b->cls.st, b->cls.state, b->cls.chi2, b->cls.uv, b->cls.idx};
-    for (void* p : cls)
-      if (p) hipFree(p);
-    if (b->cls.pinned) hipHostFree(b->cls.pinned);
-  }
+  if (b->cls.pinned) hipHostFree(b->cls.pinned);
   if (b->stream) hipStreamDestroy(b->stream);
-  delete b;
+  delete b;  // the classify pass's device buffers free themselves
   return PICP_OK;
 }
 

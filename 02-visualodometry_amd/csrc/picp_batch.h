@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "picp_c.h"
+#include "picp_host.h"
 #include "picp_internal.h"
 #include "picp_layout.h"
 
@@ -56,20 +57,13 @@ struct picp_batch : LayoutPlan {
   struct Classify {
     bool ready = false;          // the tables below describe the current layout
     int nb = 0;                  // tiles
-    void* tables = nullptr;      // int4 blk[nb] | int2 pblk[np] | int64 plane_off[np] | int64 pack_off[np]
-    int64_t tables_cap = 0;      // bytes
-    void* scan = nullptr;        // int cnt[3 nb] | int64 base[3 (nb+1)] | int64 counts[3 np] | int64 inl_off[np+1]
-    int64_t scan_cap = 0;        // bytes
-    PicpState* st = nullptr;     // np poses to classify at
-    int64_t st_cap = 0;
-    uint8_t* state = nullptr;
-    int64_t state_cap = 0;
-    float* chi2 = nullptr;
-    int64_t chi2_cap = 0;
-    float* uv = nullptr;
-    int64_t uv_cap = 0;
-    int32_t* idx = nullptr;
-    int64_t idx_cap = 0;
+    DevBuf<char> tables;         // int4 blk[nb] | int2 pblk[np] | int64 plane_off[np] | int64 pack_off[np]
+    DevBuf<char> scan;           // int cnt[3 nb] | int64 base[3 (nb+1)] | int64 counts[3 np] | int64 inl_off[np+1]
+    DevBuf<PicpState> st;        // np poses to classify at
+    DevBuf<uint8_t> state;
+    DevBuf<float> chi2;
+    DevBuf<float> uv;
+    DevBuf<int32_t> idx;
     long long* pinned = nullptr; // counts[3 np] | inl_off[np+1]
     int64_t pinned_cap = 0;      // int64 words
     std::vector<PicpState> st_h;

@@ -48,11 +48,11 @@ static int cls_prepare(picp_batch* b) {
   CHECK_ARG(nb64 <= INT32_MAX / 4, "classify: too many tiles");
   const int nb = (int)nb64;
   const ClsLayout L = cls_layout(nb, np);
-  int rc = grow(&c.tables, &c.tables_cap, L.tables_bytes, 1);
+  int rc = c.tables.grow(L.tables_bytes);
   if (rc) return rc;
-  rc = grow(&c.scan, &c.scan_cap, L.scan_bytes, 1);
+  rc = c.scan.grow(L.scan_bytes);
   if (rc) return rc;
-  rc = grow((void**)&c.st, &c.st_cap, np, sizeof(PicpState));
+  rc = c.st.grow(np);
   if (rc) return rc;
   const int64_t words = 4 * (int64_t)np + 1;
   if (words > c.pinned_cap) {
@@ -101,9 +101,9 @@ static hipError_t cls_enqueue(picp_batch* b, float threshold, bool want_chi2, bo
   char* s = (char*)c.scan;
   return picp_launch_classify(b->stream, c.nb, b->np, b->X(), b->Y(), b->Z(), b->U(), b->V(), &a,
                               (const int4*)(t + L.blk), (const int2*)(t + L.pblk), (const int64_t*)(t + L.plane_off),
-                              (const int64_t*)(t + L.pack_off), c.st, c.state, want_chi2 ? c.chi2 : nullptr,
-                              want_uv ? c.uv : nullptr, (int*)(s + L.cnt), (long long*)(s + L.base),
-                              (long long*)(s + L.counts), (long long*)(s + L.inl_off), want_idx ? c.idx : nullptr);
+                              (const int64_t*)(t + L.pack_off), c.st, c.state, want_chi2 ? c.chi2.p : nullptr,
+                              want_uv ? c.uv.p : nullptr, (int*)(s + L.cnt), (long long*)(s + L.base),
+                              (long long*)(s + L.counts), (long long*)(s + L.inl_off), want_idx ? c.idx.p : nullptr);
 }
 
 // the per-item device outputs a pass needs, and the poses (T: 16 per problem, or the batch's
@@ -112,11 +112,11 @@ static int cls_setup_pass(picp_batch* b, const float* T, bool want_chi2, bool wa
   int rc = cls_prepare(b);
   if (rc) return rc;
   picp_batch::Classify& c = b->cls;
-  rc = grow((void**)&c.state, &c.state_cap, b->total + 4, 1);
+  rc = c.state.grow(b->total + 4);
   if (rc) return rc;
-  if (want_chi2 && (rc = grow((void**)&c.chi2, &c.chi2_cap, b->total, sizeof(float)))) return rc;
-  if (want_uv && (rc = grow((void**)&c.uv, &c.uv_cap, 2 * b->total, sizeof(float)))) return rc;
-  if (want_idx && (rc = grow((void**)&c.idx, &c.idx_cap, b->total, sizeof(int32_t)))) return rc;
+  if (want_chi2 && (rc = c.chi2.grow(b->total))) return rc;
+  if (want_uv && (rc = c.uv.grow(2 * b->total))) return rc;
+  if (want_idx && (rc = c.idx.grow(b->total))) return rc;
   for (int i = 0; i < b->np; ++i) {
     if (T) {
       memset(&c.st_h[i], 0, sizeof(PicpState));

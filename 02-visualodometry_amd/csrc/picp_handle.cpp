@@ -18,12 +18,9 @@
 
 struct picp_handle {
   picp_batch* b = nullptr;
-  float* world_d = nullptr;
-  int64_t n_world = 0, cap_world = 0;
-  float* image_d = nullptr;
-  int64_t n_image = 0, cap_image = 0;
-  int2* pairs_d = nullptr;
-  int64_t cap_pairs = 0;
+  DevBuf<float> world_d, image_d;
+  int64_t n_world = 0, n_image = 0;
+  DevBuf<int2> pairs_d;
   std::vector<int32_t> pairs_h;  // cached copy of the current correspondences
   int64_t m = -1;                // -1: none set
   bool have_points = false;
@@ -56,11 +53,8 @@ extern "C" int picp_destroy(picp_t* h) {
     hipSetDevice(h->b->device);
     hipStreamSynchronize(h->b->stream);
   }
-  if (h->world_d) hipFree(h->world_d);
-  if (h->image_d) hipFree(h->image_d);
-  if (h->pairs_d) hipFree(h->pairs_d);
   picp_batch_destroy(h->b);
-  delete h;
+  delete h;  // the device buffers free themselves
   return PICP_OK;
 }
 
@@ -91,9 +85,9 @@ extern "C" int picp_clone(const picp_t* src, picp_t** out) {
   };
   if (src->have_points) {
     HIP_TRY(hipSetDevice(sb->device));
-    rc = grow((void**)&h->world_d, &h->cap_world, 3 * src->n_world, sizeof(float));
+    rc = h->world_d.grow(3 * src->n_world);
     if (rc) return fail(rc);
-    rc = grow((void**)&h->image_d, &h->cap_image, 2 * src->n_image, sizeof(float));
+    rc = h->image_d.grow(2 * src->n_image);
     if (rc) return fail(rc);
     // the source's stream is drained first: its uploads may still be in flight
     hipError_t e = hipStreamSynchronize(sb->stream);
@@ -122,9 +116,9 @@ extern "C" int picp_set_points(picp_t* h, const float* world, int64_t n_world, c
   CHECK_ARG(n_world >= 0 && n_image >= 0, "picp_set_points: negative size");
   CHECK_ARG((n_world == 0 || world) && (n_image == 0 || image), "picp_set_points: null array");
   HIP_TRY(hipSetDevice(h->b->device));
-  int rc = grow((void**)&h->world_d, &h->cap_world, 3 * n_world, sizeof(float));
+  int rc = h->world_d.grow(3 * n_world);
   if (rc) return rc;
-  rc = grow((void**)&h->image_d, &h->cap_image, 2 * n_image, sizeof(float));
+  rc = h->image_d.grow(2 * n_image);
   if (rc) return rc;
   if (n_world) HIP_TRY(hipMemcpyAsync(h->world_d, world, (size_t)n_world * 3 * sizeof(float), hipMemcpyHostToDevice, h->b->stream));
   if (n_image) HIP_TRY(hipMemcpyAsync(h->image_d, image, (size_t)n_image * 2 * sizeof(float), hipMemcpyHostToDevice, h->b->stream));
@@ -159,7 +153,7 @@ static int handle_prepare(picp_handle* h) {
     if (rc) return rc;
   }
   if (h->m > 0) {
-    int rc = grow((void**)&h->pairs_d, &h->cap_pairs, h->m, sizeof(int2));
+    int rc = h->pairs_d.grow(h->m);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h->pairs_d, h->pairs_h.data(), (size_t)h->m * sizeof(int2), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(picp_launch_gather(b->stream, h->world_d, h->image_d, h->pairs_d, h->m, b->X(), b->Y(), b->Z(), b->U(), b->V(), b->plane_off[0]));

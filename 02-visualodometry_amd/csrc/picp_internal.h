@@ -14,7 +14,7 @@
 #include <stdint.h>
 
 #include "picp_c.h"        // picp_stats
-#include "picp_problem.h"  // PICP_BLOCK, PICP_NPART, PICP_POSE_SETS, PicpProblem
+#include "picp_problem.h"  // PICP_BLOCK, PICP_NPART, PICP_POSE_SETS, PicpProblem, MatchProblem, VoSegment
 
 // partial slot layout
 #define PICP_P_H 0                // 21 upper-triangle entries of H (row-major upper)
@@ -123,8 +123,7 @@ static_assert(sizeof(RefinePose) == 48, "RefinePose must be 48 B");
 static_assert(sizeof(PicpState) == 128, "PicpState must be 128 B");
 
 // ---------------------------------------------------------------------------------------
-// descriptor matching (picp_match.hip): query rows [q_off, q_off + nq) of the query
-// descriptors against reference rows [r_off, r_off + nr); best_idx is relative to r_off.
+// descriptor matching (picp_match.hip; MatchProblem: picp_problem.h).
 // Every PICP device translation unit is compiled WITHOUT packed-FP32 VALU instructions
 // (v_pk_fma/mul/add_f32): hipcc_nopk.sh passes -target-feature -packed-fp32-ops to the whole
 // device compile.  On MI355X (gfx950, ROCm 7.2) the compiler's packed code for apply_update gave
@@ -135,13 +134,6 @@ static_assert(sizeof(PicpState) == 128, "PicpState must be 128 B");
 // the matcher ran beside the block kernel.  The flag is TU-wide on purpose: a
 // per-kernel target("no-packed-fp32-ops") attribute stops HIP's header functions (__syncthreads,
 // ...) from inlining into the kernel, and the calls cost C2 18 % and C5 80 % (round-3 pass).
-
-struct MatchProblem {
-  int64_t q_off, nq, r_off, nr;
-  // the index of reference r_off in the caller's numbering (0: indices relative to r_off): a
-  // problem over a later part of a reference set reports indices in the whole set's numbering
-  int64_t idx0;
-};
 
 // ---------------------------------------------------------------------------------------
 // essential-matrix bootstrap (picp_essential.hip; src/cam.cpp:37-91), by value
@@ -155,15 +147,7 @@ struct EssArgs {
 };
 
 // ---------------------------------------------------------------------------------------
-// device-resident VO sequence (picp_vo.hip): exec/icp_test.cpp:36-136 per segment
-struct VoSegment {
-  int64_t f0;       // first frame of the segment (bootstrap pair = f0, f0+1)
-  int64_t map_off;  // first map slot of the segment
-  int64_t slot0;    // first pose / step-record slot (steps + 1 slots)
-  int32_t steps;    // PICP steps (frames f0+1 .. f0+steps are estimated)
-  int32_t pad;
-};
-
+// device-resident VO sequence (picp_vo.hip; VoSegment: picp_problem.h)
 struct VoStep {     // per pose slot; slot 0 of a segment = the bootstrap
   int32_t n_corr;   // map correspondences of the frame (PICP input size)
   int32_t n_in;     // inliers of the last PICP round

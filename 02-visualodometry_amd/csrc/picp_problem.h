@@ -1,5 +1,5 @@
-// picp_problem.h -- the part of the device-visible layout (picp_internal.h) that the layout plan
-// (picp_layout.h) shares with the kernels.  Plain C: no HIP type.
+// picp_problem.h -- the part of the device-visible layout (picp_internal.h) that the layout plans
+// (picp_layout.h, picp_vo_plan.h) share with the kernels.  Plain C: no HIP type.
 #pragma once
 #include <stdint.h>
 
@@ -18,3 +18,23 @@ struct PicpProblem {
   int32_t pad;
 };
 static_assert(sizeof(PicpProblem) % 8 == 0, "PicpProblem alignment");
+
+// descriptor matching (picp_match.hip): query rows [q_off, q_off + nq) of the query
+// descriptors against reference rows [r_off, r_off + nr); best_idx is relative to r_off.
+struct MatchProblem {
+  int64_t q_off, nq, r_off, nr;
+  // the index of reference r_off in the caller's numbering (0: indices relative to r_off): a
+  // problem over a later part of a reference set reports indices in the whole set's numbering
+  int64_t idx0;
+};
+static_assert(sizeof(MatchProblem) == 40, "MatchProblem must be 40 B");
+
+// device-resident VO sequence (picp_vo.hip): exec/icp_test.cpp:36-136 per segment
+struct VoSegment {
+  int64_t f0;       // first frame of the segment (bootstrap pair = f0, f0+1)
+  int64_t map_off;  // first map slot of the segment
+  int64_t slot0;    // first pose / step-record slot (steps + 1 slots)
+  int32_t steps;    // PICP steps (frames f0+1 .. f0+steps are estimated)
+  int32_t pad;
+};
+static_assert(sizeof(VoSegment) == 32, "VoSegment must be 32 B");

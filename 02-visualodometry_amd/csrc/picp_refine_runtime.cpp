@@ -51,11 +51,8 @@ extern "C" int picp_refine_destroy(picp_refine_t* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   adjust_free(h);
-  void* bufs[] = {h->poses_d, h->off_d, h->obs_pose_d, h->obs_uv_d, h->xyz_d, h->xyz0_d, h->stats_d};
-  for (void* p : bufs)
-    if (p) hipFree(p);
   if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // the device buffers free themselves
   return PICP_OK;
 }
 
@@ -71,8 +68,8 @@ extern "C" int picp_refine_set_poses(picp_refine_t* h, const float* T_wc, int n_
     tab[k].r1 = make_float4(T[1], T[5], T[9], T[13]);
     tab[k].r2 = make_float4(T[2], T[6], T[10], T[14]);
   }
-  int rc = grow((void**)&h->poses_d, &h->cap_poses, n_poses, sizeof(RefinePose));
-  if (!rc) rc = grow((void**)&h->adj.T_d, &h->adj.cap_T, 16 * (int64_t)n_poses, sizeof(float));
+  int rc = h->poses_d.grow(n_poses);
+  if (!rc) rc = h->adj.T_d.grow(16 * (int64_t)n_poses);
   if (rc) return rc;
   if (n_poses) {
     HIP_TRY(hipMemcpyAsync(h->poses_d, tab.data(), (size_t)n_poses * sizeof(RefinePose), hipMemcpyHostToDevice, h->stream));
@@ -104,9 +101,9 @@ extern "C" int picp_refine_set_tracks(picp_refine_t* h, int64_t n_points, const 
     max_idx = std::max(max_idx, obs_pose[k]);
   }
   HIP_TRY(hipSetDevice(h->device));
-  int rc = grow((void**)&h->off_d, &h->cap_off, n_points + 1, sizeof(int64_t));
-  if (!rc) rc = grow((void**)&h->obs_pose_d, &h->cap_obs_pose, n_obs, sizeof(int32_t));
-  if (!rc) rc = grow((void**)&h->obs_uv_d, &h->cap_obs_uv, n_obs, sizeof(float2));
+  int rc = h->off_d.grow(n_points + 1);
+  if (!rc) rc = h->obs_pose_d.grow(n_obs);
+  if (!rc) rc = h->obs_uv_d.grow(n_obs);
   if (rc) {
     h->n_points = -1;
     return rc;
@@ -133,7 +130,7 @@ extern "C" int picp_refine_set_points(picp_refine_t* h, const float* xyz) {
   if (h->n_points < 0) return set_err(PICP_ERR_STATE, "picp_refine_set_points: tracks not set (they give n_points)");
   CHECK_ARG(h->n_points == 0 || xyz, "picp_refine_set_points: null array");
   HIP_TRY(hipSetDevice(h->device));
-  int rc = grow((void**)&h->xyz_d, &h->cap_xyz, 3 * h->n_points, sizeof(float));
+  int rc = h->xyz_d.grow(3 * h->n_points);
   if (rc) return rc;
   if (h->n_points) {
     HIP_TRY(hipMemcpyAsync(h->xyz_d, xyz, (size_t)h->n_points * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -155,19 +152,9 @@ int refine_prepare(picp_refine* h, const picp_refine_params* prm, RefineArgs* a)
     return set_err(PICP_ERR_RANGE, "refine: the tracks use pose index %d but %d poses are set", h->max_pose_idx,
                    h->n_poses);
   HIP_TRY(hipSetDevice(h->device));
-  int rc = grow((void**)&h->stats_d, &h->cap_stats, h->n_points, sizeof(picp_stats));
+  int rc = h->stats_d.grow(h->n_points);
   if (rc) return rc;
-  memcpy(a->K, h->K, sizeof(a->K));
-  a->maxx = (float)(h->cols - 1);
-  a->maxy = (float)(h->rows - 1);
-  a->threshold = prm->threshold;
-  a->damping = prm->damping;
-  a->conv_eps = prm->conv_eps;
-  a->min_inliers = prm->min_inliers;
-  a->keep_outliers = prm->keep_outliers;
-  a->max_rounds = prm->max_rounds;
-  a->pinhole = 0;
-  a->n_points = h->n_points;
+  refine_fill_args(h->K, h->rows, h->cols, prm, h->n_points, a);
   return PICP_OK;
 }
 
@@ -218,26 +205,21 @@ extern "C" int picp_refine_time(picp_refine_t* h, const picp_refine_params* prm,
     h->have_stats = true;
     return PICP_OK;
   }
-  rc = grow((void**)&h->xyz0_d, &h->cap_xyz0, 3 * h->n_points, sizeof(float));
+  rc = h->xyz0_d.grow(3 * h->n_points);
   if (rc) return rc;
   const size_t bytes = (size_t)h->n_points * 3 * sizeof(float);
   HIP_TRY(hipMemcpyAsync(h->xyz0_d, h->xyz_d, bytes, hipMemcpyDeviceToDevice, h->stream));
   // every repetition: restore (untimed), event, launch, event; one wait at the end
-  std::vector<EventPair> ev((size_t)reps);
-  for (auto& e : ev) HIP_TRY(e.create());
+  TimedSpans ev(reps);
+  HIP_TRY(ev.create());
   for (int r = 0; r < reps; ++r) {
     HIP_TRY(hipMemcpyAsync(h->xyz_d, h->xyz0_d, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipEventRecord(ev[r].a, h->stream));
+    HIP_TRY(ev.begin(r, h->stream));
     HIP_TRY(refine_enqueue(h, &a));
-    HIP_TRY(hipEventRecord(ev[r].b, h->stream));
+    HIP_TRY(ev.end(r, h->stream));
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
   double total_ms = 0.0;
-  for (int r = 0; r < reps; ++r) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[r].a, ev[r].b));
-    total_ms += ms;
-  }
+  HIP_TRY(ev.sum_ms(h->stream, &total_ms));
   *us_per_run = (float)(1000.0 * total_ms / reps);
   h->have_stats = true;
   return PICP_OK;
