@@ -26,6 +26,10 @@
 
 #include "picp_c.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_wave.h"
+
+using namespace picp;
 
 #define AJ_BLOCK 256
 #define AJ_SCAN 1024
@@ -44,27 +48,14 @@ __global__ __launch_bounds__(AJ_BLOCK) void adj_count_kernel(const AdjView v) {
 
 __global__ __launch_bounds__(AJ_SCAN) void adj_scan_kernel(const AdjView v) {
   __shared__ int s_w[AJ_SCAN_WAVES];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int64_t carry = 0;
   for (int64_t c0 = 0; c0 < v.n_poses; c0 += AJ_SCAN) {  // uniform
     const int64_t j = c0 + threadIdx.x;
     const int c = j < v.n_poses ? v.cnt[j] : 0;
-    int x = c;
-#pragma unroll
-    for (int d = 1; d < 64; d *= 2) {
-      const int y = __shfl_up(x, d);
-      x += lane >= d ? y : 0;
-    }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < AJ_SCAN_WAVES; ++k) {
-      pre += (k < w) ? s_w[k] : 0;
-      tot += s_w[k];
-    }
+    int tot;
+    const int excl = block_scan<AJ_SCAN_WAVES>(c, s_w, &tot);
     if (j < v.n_poses) {
-      v.pose_off[j] = carry + pre + x - c;
+      v.pose_off[j] = carry + excl;
       v.cnt[j] = 0;  // the fill's cursor
     }
     carry += tot;
@@ -137,11 +128,8 @@ __global__ __launch_bounds__(AJ_BLOCK) void adj_gather_kernel(const AdjPose g, i
   }
   if (threadIdx.x == 0) {
     // the state picp_batch_set_poses leaves: the pose, and the loop state at entry
-    const RefinePose P = g.rposes[k];
     PicpState s = {};
-    s.R[0] = P.r0.x; s.R[3] = P.r0.y; s.R[6] = P.r0.z; s.t[0] = P.r0.w;
-    s.R[1] = P.r1.x; s.R[4] = P.r1.y; s.R[7] = P.r1.z; s.t[1] = P.r1.w;
-    s.R[2] = P.r2.x; s.R[5] = P.r2.y; s.R[8] = P.r2.z; s.t[2] = P.r2.w;
+    rows_to_state(g.rposes[k], s);
     s.chi_prev = FLT_MAX;
     s.ok = 1;
     g.init[p] = s;
@@ -169,23 +157,8 @@ __global__ __launch_bounds__(AJ_BLOCK) void adj_writeback_kernel(const AdjPose g
   o.reserved = 0;
   g.pose_stats[k] = o;
   if (!finite) return;  // the pose keeps its value
-  RefinePose P;
-  P.r0 = make_float4(s.R[0], s.R[3], s.R[6], s.t[0]);
-  P.r1 = make_float4(s.R[1], s.R[4], s.R[7], s.t[1]);
-  P.r2 = make_float4(s.R[2], s.R[5], s.R[8], s.t[2]);
-  g.rposes[k] = P;
-  float* T = g.T + 16 * (int64_t)k;  // state_to_pose
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    T[4 * j + 0] = s.R[3 * j + 0];
-    T[4 * j + 1] = s.R[3 * j + 1];
-    T[4 * j + 2] = s.R[3 * j + 2];
-    T[4 * j + 3] = 0.0f;
-  }
-  T[12] = s.t[0];
-  T[13] = s.t[1];
-  T[14] = s.t[2];
-  T[15] = 1.0f;
+  g.rposes[k] = state_to_rows(s);
+  state_to_pose(s, g.T + 16 * (int64_t)k);
 }
 
 // thread t adds items t, t + AJ_SCAN, ... in that order; then a fixed binary tree over the threads

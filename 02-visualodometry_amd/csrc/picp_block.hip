@@ -5,7 +5,7 @@
 // per lane); any remainder is re-read every round (two per lane per step, L2/MALL-resident
 // after the first round).  Every round is: linearize in registers -> wave64 reduction (permlane/DPP) -> LDS
 // combine of the 8 waves -> wave 0 finishes the round (fp32 LDL^T, Rx*Ry*Rz update,
-// convergence; picp_device.h finish_round_pose, every lane the same values, the loop state in
+// convergence; picp_solve6.h finish_round_pose, every lane the same values, the loop state in
 // registers) -> barrier.  No inter-workgroup communication at all, no launch
 // per round and no HBM re-read per round: a batch of frames is bound by VALU issue, not by
 // hand-off latency or HBM.  Ragged batches read (offset, n) from the problem
@@ -28,8 +28,12 @@
 // one problem's parts exchange and solve (the CU idle in split = 2), the other's compute.
 #include <type_traits>
 
-#include "picp_vo_device.h"
+#include "picp_item.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_solve6.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -319,11 +323,7 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
   __syncthreads();
 
   Cam C;
-  C.k00 = A.K[0]; C.k10 = A.K[1]; C.k20 = A.K[2];
-  C.k01 = A.K[3]; C.k11 = A.K[4]; C.k21 = A.K[5];
-  C.k02 = A.K[6]; C.k12 = A.K[7]; C.k22 = A.K[8];
-  C.maxx = A.maxx;
-  C.maxy = A.maxy;
+  cam_load(A.K, A.maxx, A.maxy, C);
   const float thr = A.threshold;
   const float inv_thr = 1.0f / thr;
   const bool keep = A.keep_outliers != 0;
@@ -340,11 +340,8 @@ __global__ __launch_bounds__(BS, MINW) void picp_block_kernel(
     // step kernel within noise (profiles/r04/c4_128/, profiles/r04/pair2/).
     __builtin_amdgcn_s_setprio(0);
     Pose T;
-    T.r00 = s_pose[0]; T.r10 = s_pose[1]; T.r20 = s_pose[2];
-    T.r01 = s_pose[3]; T.r11 = s_pose[4]; T.r21 = s_pose[5];
-    T.r02 = s_pose[6]; T.r12 = s_pose[7]; T.r22 = s_pose[8];
-    T.t0 = s_pose[9]; T.t1 = s_pose[10]; T.t2 = s_pose[11];
-    // accumulation form by register-resident items per lane (picp_device.h acc_pairs): two slots
+    pose_load(s_pose, s_pose + 9, T);
+    // accumulation form by register-resident items per lane (picp_item.h acc_pairs): two slots
     // for NPT 8, one slot below
     float v[PICP_NPART];
     Cnt nr = {0u, 0u}, nd = {0u, 0u};  // counts: register items (uniform), divergent loops (lane 0)

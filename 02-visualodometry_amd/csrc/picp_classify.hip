@@ -17,8 +17,11 @@
 //
 //   vo_track_kernel      : the VO sequence's per-map-point counters: one block per segment over
 //                          the step's frame->map matches (shaped like vo_gather_kernel).
-#include "picp_device.h"
+#include "picp_item.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -28,21 +31,6 @@ using namespace picp;
 #define CLS_SCAN_BLOCK 1024
 #define CLS_SCAN_WAVES (CLS_SCAN_BLOCK / 64)
 #define CLS_SCAN_PER 8  // consecutive tiles per lane and round of the scan
-
-__device__ __forceinline__ void cls_pose(const PicpState* st, Pose& T) {
-  T.r00 = st->R[0]; T.r10 = st->R[1]; T.r20 = st->R[2];
-  T.r01 = st->R[3]; T.r11 = st->R[4]; T.r21 = st->R[5];
-  T.r02 = st->R[6]; T.r12 = st->R[7]; T.r22 = st->R[8];
-  T.t0 = st->t[0]; T.t1 = st->t[1]; T.t2 = st->t[2];
-}
-
-__device__ __forceinline__ void cls_cam(const float K[9], float maxx, float maxy, Cam& C) {
-  C.k00 = K[0]; C.k10 = K[1]; C.k20 = K[2];
-  C.k01 = K[3]; C.k11 = K[4]; C.k21 = K[5];
-  C.k02 = K[6]; C.k12 = K[7]; C.k22 = K[8];
-  C.maxx = maxx;
-  C.maxy = maxy;
-}
 
 // blk[b] = (problem, first item of the tile inside the problem, items in the tile, -);
 // plane_off[p] / pack_off[p] = the problem's first item in the planes (a multiple of 4) and in the
@@ -61,8 +49,8 @@ __global__ __launch_bounds__(CLS_BLOCK) void picp_classify_kernel(
   const int64_t obase = pack_off[bi.x] + bi.y;
   Pose T;
   Cam C;
-  cls_pose(st + bi.x, T);
-  cls_cam(a.K, a.maxx, a.maxy, C);
+  pose_load(st[bi.x].R, st[bi.x].t, T);
+  cam_load(a.K, a.maxx, a.maxy, C);
   const int i0 = 4 * (int)threadIdx.x;
   float x[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0}, z[4] = {0, 0, 0, 0}, u[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
   if (i0 < n) {  // planes are padded to a multiple of 4 per problem: the whole float4 is in bounds
@@ -131,16 +119,6 @@ __global__ __launch_bounds__(CLS_BLOCK) void picp_classify_kernel(
   }
 }
 
-// inclusive scan over the wave's lanes
-__device__ __forceinline__ int cls_wave_scan(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    v += (lane >= d) ? o : 0;
-  }
-  return v;
-}
-
 // One block.  base[c * (nb + 1) + b] = the number of class-c items in tiles 0 .. b-1 (entry nb:
 // the batch's total).  pblk[p] = (first tile, tiles) of problem p: its counts and its first
 // inlier's position are differences / entries of the scan.
@@ -171,7 +149,7 @@ __global__ __launch_bounds__(CLS_SCAN_BLOCK) void picp_classify_scan_kernel(
     int excl[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const int inc = cls_wave_scan(sum[c], lane);
+      const int inc = wave_scan(sum[c], lane);
       if (lane == 63) s_w[c][w] = inc;
       excl[c] = inc - sum[c];
     }
@@ -179,12 +157,8 @@ __global__ __launch_bounds__(CLS_SCAN_BLOCK) void picp_classify_scan_kernel(
     long long run[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      int pre = 0, tot = 0;
-#pragma unroll
-      for (int k = 0; k < CLS_SCAN_WAVES; ++k) {
-        pre += (k < w) ? s_w[c][k] : 0;
-        tot += s_w[c][k];
-      }
+      int pre, tot;
+      wave_totals<CLS_SCAN_WAVES>(s_w[c], w, &pre, &tot);
       run[c] = carry[c] + pre + excl[c];
       carry[c] += tot;
     }
@@ -276,8 +250,8 @@ __global__ __launch_bounds__(CLS_BLOCK) void vo_track_kernel(const VoArgs a, int
   const int64_t moff = G.map_off;
   Pose T;
   Cam C;
-  cls_pose(a.st_out + s, T);
-  cls_cam(c.K, c.maxx, c.maxy, C);
+  pose_load(a.st_out[s].R, a.st_out[s].t, T);
+  cam_load(c.K, c.maxx, c.maxy, C);
   for (int64_t i = threadIdx.x; i < nn; i += CLS_BLOCK) {
     if (a.wm_acc[on + i] == 0) continue;
     const int64_t j = moff + a.wm_bi[on + i];

@@ -257,7 +257,7 @@ extern "C" int picp_match(int device, const float* desc1, int64_t n1, const floa
 }
 
 // ------------------------------------------------------------------------------------
-// self-test: the fast correctly rounded reciprocal of the projection (picp_device.h rcp_rn)
+// self-test: the fast correctly rounded reciprocal of the projection (picp_recip.h rcp_rn)
 // ------------------------------------------------------------------------------------
 extern "C" int picp_selftest_rcp(int device, int e_lo, int e_hi, uint64_t* mismatches) {
   CHECK_ARG(mismatches && e_lo >= -126 && e_hi <= 127 && e_lo < e_hi, "picp_selftest_rcp: bad argument");
@@ -275,7 +275,7 @@ extern "C" int picp_selftest_rcp(int device, int e_lo, int e_hi, uint64_t* misma
 }
 
 // ------------------------------------------------------------------------------------
-// self-test: the lane-parallel finish of a round against the uniform one (picp_device.h)
+// self-test: the lane-parallel finish of a round against the uniform one (picp_solve6.h)
 // ------------------------------------------------------------------------------------
 extern "C" int picp_selftest_finish(int device, int64_t n_cases, const uint32_t* cases, uint64_t* mismatches,
                                     uint32_t* out) {

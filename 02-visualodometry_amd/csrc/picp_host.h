@@ -8,15 +8,17 @@
 
 #include "picp_c.h"
 #include "picp_internal.h"
+#include "picp_pose.h"
 
 #pragma GCC visibility push(hidden)
 
 // records the thread's last error message (picp_last_error) and returns `code`
 __attribute__((format(printf, 2, 3))) int picp_set_err(int code, const char* fmt, ...);
 
-// pose helpers (column-major 4x4 <-> state R(col-major 3x3), t), picp_runtime.cpp
-void pose_to_state(const float T[16], PicpState& s);
-void state_to_pose(const PicpState& s, float T[16]);
+// the pose conversions the host calls (picp_pose.h)
+using picp::pose_to_state;
+using picp::state_to_pose;
+// picp_runtime.cpp
 void state_to_stats(const PicpState& s, picp_stats& st);
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }

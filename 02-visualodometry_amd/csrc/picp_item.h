@@ -1,38 +1,19 @@
-// picp_device.h -- device-side math shared by the PICP kernels (picp_kernels.hip, multi-launch
-// rounds; picp_persistent.hip, single-launch rounds): per-correspondence projection/Jacobian/gate
-// (src/camera.h:24-36, src/picp_solver.cpp:26-91), the wave64 normal-equation reduction, the
-// damped 6x6 LDL^T solve and the v2tEuler left update (src/picp_solver.cpp:93-105,
-// src/defs.h:100-136), and the icp_test convergence rule (exec/icp_test.cpp:99-106).
+// picp_item.h -- the per-correspondence math of the PICP solve: projection, Jacobian and chi2 gate
+// (src/camera.h:24-36, src/picp_solver.cpp:26-91) in every accumulation form the kernels use, and
+// the observers' restatement of the gate (classify_item).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <float.h>
-#include <stdlib.h>
-#include <stdint.h>
 
 #include <type_traits>
 
 #include "picp_internal.h"
+#include "picp_pose.h"
+#include "picp_recip.h"
+#include "picp_variant.h"
 
 namespace picp {
-
-struct Pose {
-  float r00, r01, r02, r10, r11, r12, r20, r21, r22;
-  float t0, t1, t2;
-};
-
-struct Cam {
-  float k00, k01, k02, k10, k11, k12, k20, k21, k22;
-  float maxx, maxy;  // cols-1, rows-1 (src/camera.h:31,33)
-};
-
-// Per-item math variant, fixed at launch (picp_variant): any K with the kernel weight chosen at
-// run time; the reference's pinhole K with outliers rejected (keep_outliers = false, as
-// icp_test runs it: every used item has weight exactly 1, so the weighted Jacobian IS the
-// Jacobian and no weight is formed); pinhole K with outliers kept (robust weight per item).
-#define PICP_V_GENERAL 0
-#define PICP_V_PINHOLE 1
-#define PICP_V_PINHOLE_KEEP 2
 
 struct Acc {
   float h[21];  // upper triangle of H, row-major (i<=j)
@@ -96,22 +77,6 @@ __device__ __forceinline__ void acc2_fold(const Acc2& a, float v[PICP_NPART]) {
   v[PICP_P_N_IN] = 0.0f;
   v[PICP_P_N_PROJ] = 0.0f;
   v[31] = 0.0f;
-}
-
-// Correctly rounded 1/x in 3 instructions: v_rcp_f32 (about 1 ulp) and one FMA Newton step.
-// Verified bit-identical to the IEEE division 1.0f/x for EVERY float x in [2^-8, 2^8) by
-// picp_selftest_rcp (tests/test_gpu_parity.py); both operations are exact under power-of-two
-// scaling inside the normal range, so that covers every x with 2^-100 <= |x| <= 2^100
-// (rcp_safe).  Outside it (and for 0, inf, NaN) callers use the IEEE division.
-__device__ __forceinline__ float rcp_rn(float x) {
-  const float r = __builtin_amdgcn_rcpf(x);
-  const float e = fmaf(-x, r, 1.0f);
-  return fmaf(e, r, r);
-}
-
-__device__ __forceinline__ bool rcp_safe(float x) {
-  const float a = fabsf(x);
-  return (a >= 7.8886091e-31f) & (a <= 1.2676506e30f);  // [2^-100, 2^100]; NaN -> false
 }
 
 // ---------------------------------------------------------------------------------------
@@ -754,609 +719,6 @@ __device__ __forceinline__ void accumulate(const Pose& T, const Cam& C, float th
     accumulate_one(T, C, thr, keep, x, y, z, u, v, in_range, a, n);
   else
     accumulate_pinhole<PH == PICP_V_PINHOLE_KEEP>(T, C, thr, inv_thr, x, y, z, u, v, in_range, a, n);
-}
-
-__host__ __device__ inline bool is_pinhole(const float K[9]) {  // column-major K
-  return K[1] == 0.0f && K[2] == 0.0f && K[3] == 0.0f && K[5] == 0.0f && K[8] == 1.0f;
-}
-
-}  // namespace picp
-
-// launch-time camera path: pinhole unless K is general or PICP_FORCE_GENERAL_K=1 (A/B checks)
-inline bool picp_use_pinhole(const float K[9]) {
-  static const bool force_general = [] {
-    const char* e = getenv("PICP_FORCE_GENERAL_K");
-    return e && atoi(e) != 0;
-  }();
-  return !force_general && picp::is_pinhole(K);
-}
-
-// launch-time per-item variant (PICP_V_*): the camera path, and for the pinhole path whether
-// outliers are kept (a compile-time weight)
-inline int picp_variant(const float K[9], int keep_outliers) {
-  if (!picp_use_pinhole(K)) return PICP_V_GENERAL;
-  return keep_outliers ? PICP_V_PINHOLE_KEEP : PICP_V_PINHOLE;
-}
-
-namespace picp {
-
-// Cross-lane moves without the LDS crossbar.  gfx950 v_permlane32_swap / v_permlane16_swap
-// exchange half-waves / odd-even 16-lane rows between two registers; DPP reads a partner
-// lane inside a 16-lane row (row_mirror l^15, row_half_mirror l^7, quad_perm l^2, l^1).
-// bound_ctrl on: a lane whose source lane is disabled in EXEC reads 0, so the result never depends
-// on the destination's old contents (every call site runs with EXEC full, where no source lane is
-// disabled).  Passing the source as DPP "old" instead (round 4) tied the destination to it and
-// cost a register copy per move: C2/C3 1-2 % slower in interleaved A/B (profiles/r05/ab_regress/).
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-#define DPP_ROW_MIRROR 0x140
-#define DPP_ROW_HALF_MIRROR 0x141
-#define DPP_QUAD_XOR2 0x4E  // quad_perm [2,3,0,1]
-#define DPP_QUAD_XOR1 0xB1  // quad_perm [1,0,3,2]
-
-// Halving-butterfly step inside a 16-lane row: lanes l and P(l) (P an involution that flips
-// bit HB) exchange the half of the 2*HALF values the other keeps.
-template <int CTRL, int HB, int HALF>
-__device__ __forceinline__ void bfly_dpp(float* v, int lane) {
-  const bool hi = (lane >> HB) & 1;
-#pragma unroll
-  for (int i = 0; i < HALF; ++i) {
-    const float send = hi ? v[i] : v[i + HALF];
-    const float keep = hi ? v[i + HALF] : v[i];
-    v[i] = keep + dpp<CTRL>(send);
-  }
-}
-
-// Sum 32 per-lane values over the 64 lanes of a wave (32 -> 16 -> 8 -> 4 -> 2 -> 1 values per
-// lane).  The swap steps need no select: after v_permlane32_swap(a=v[i], b=v[i+16]) the low
-// half holds (own v[i], partner v[i]) and the high half (partner v[i+16], own v[i+16]), so a+b
-// is the pair sum of the half each lane keeps.  Returns, in every lane, the wave total of value
-// index (lane >> 1).
-__device__ __forceinline__ float wave_reduce32_bperm(float* v, int lane) {
-  // the half-wave exchanges through ds_bpermute (bit-identical sums in the same order)
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const bool hi = (lane & 32) != 0;
-    const float send = hi ? v[i] : v[i + 16], keep = hi ? v[i + 16] : v[i];
-    v[i] = keep + __shfl_xor(send, 32);
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const bool hi = (lane & 16) != 0;
-    const float send = hi ? v[i] : v[i + 8], keep = hi ? v[i + 8] : v[i];
-    v[i] = keep + __shfl_xor(send, 16);
-  }
-  bfly_dpp<DPP_ROW_MIRROR, 3, 4>(v, lane);
-  bfly_dpp<DPP_ROW_HALF_MIRROR, 2, 2>(v, lane);
-  bfly_dpp<DPP_QUAD_XOR2, 1, 1>(v, lane);
-  return v[0] + dpp<DPP_QUAD_XOR1>(v[0]);
-}
-
-__device__ __forceinline__ float wave_reduce32(float* v, int lane) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 16]), false, false);
-    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 8]), false, false);
-    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  bfly_dpp<DPP_ROW_MIRROR, 3, 4>(v, lane);
-  bfly_dpp<DPP_ROW_HALF_MIRROR, 2, 2>(v, lane);
-  bfly_dpp<DPP_QUAD_XOR2, 1, 1>(v, lane);
-  return v[0] + dpp<DPP_QUAD_XOR1>(v[0]);
-}
-
-// x + (x of the lane 16, or 32, away) for a double, through the swaps of wave_reduce32 on its two
-// halves (no LDS round trip, unlike __shfl_xor's ds_bpermute).  With both operands x, the swap
-// leaves (own, partner) in one half of the pair and (partner, own) in the other: the sum is
-// own + partner or partner + own, the same bits (IEEE addition commutes).
-template <int DIST>
-__device__ __forceinline__ double wave_add_xor_f64(double x) {
-  static_assert(DIST == 16 || DIST == 32, "the two swap distances");
-  const unsigned lo = (unsigned)__double_as_longlong(x), hi = (unsigned)(__double_as_longlong(x) >> 32);
-  unsigned a_lo, a_hi, b_lo, b_hi;
-  if constexpr (DIST == 16) {
-    const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    a_lo = rl[0]; b_lo = rl[1]; a_hi = rh[0]; b_hi = rh[1];
-  } else {
-    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    a_lo = rl[0]; b_lo = rl[1]; a_hi = rh[0]; b_hi = rh[1];
-  }
-  const double a = __longlong_as_double((long long)(((unsigned long long)a_hi << 32) | a_lo));
-  const double b = __longlong_as_double((long long)(((unsigned long long)b_hi << 32) | b_lo));
-  return a + b;
-}
-
-// 1/d in float: hardware v_rcp_f32 estimate refined by one Newton step (<= 1 ulp for normal
-// d); |d| <= FLT_MIN -> 0 (Eigen's LDLT zero-pivot rule for float, src/picp_solver.cpp:102).
-__device__ __forceinline__ float rcp32(float d) {
-  float r = __builtin_amdgcn_rcpf(d);
-  r = fmaf(r, fmaf(-d, r, 1.0f), r);
-  return (fabsf(d) > FLT_MIN) ? r : 0.0f;
-}
-
-// Damped normal equations -> dx, in float32, the precision the reference solves in
-// (Matrix6f::ldlt, src/picp_solver.cpp:102); H and b arrive as exact double sums.  LDL^T without
-// pivoting, by Gaussian elimination on the LOWER triangle (H + damping*I is SPD: Eigen's diagonal
-// pivoting only changes rounding): step j scales column j by 1/d_j and updates the trailing
-// lower triangle; the back substitution reads U = D L^T from the lower entries (symmetry).  Pivot
-// reciprocals are the hardware v_rcp_f32 (<= 1 ulp).  A pivot with |d| <= FLT_MIN gives 1/d = 0,
-// Eigen's zero-pivot rule for float; that test is kept off the pivot chain (a flag, and the rare
-// flagged system is solved again with the guard in the chain).  One lane, registers only, every
-// index compile-time: the per-round critical path of every kernel (tools/ubench/parts_ubench).
-// Row r of the system is read from the converted totals tw (total_word: damping folded into the
-// diagonal, -b), upper triangle row-major.
-__device__ __forceinline__ int tri_index(int r, int c) {  // upper-triangle slot of (min, max)
-  const int lo = r < c ? r : c, hi = r < c ? c : r;
-  return PICP_P_H + lo * (11 - lo) / 2 + hi;
-}
-
-template <bool GUARD>
-__device__ __forceinline__ bool ldl6_solve(const float* tw, float dx[6]) {
-  float a[6][6], rhs[6], id[6];
-  bool bad = false;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int c = 0; c <= i; ++c) a[i][c] = tw[tri_index(c, i)];
-    rhs[i] = tw[PICP_P_B + i];
-  }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const float d = a[j][j];
-    float inv = __builtin_amdgcn_rcpf(d);
-    if (GUARD) inv = (fabsf(d) > FLT_MIN) ? inv : 0.0f;
-    else bad |= !(fabsf(d) > FLT_MIN);
-    id[j] = inv;
-    float f[6];
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) f[i] = a[i][j] * inv;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-#pragma unroll
-      for (int c = j + 1; c <= i; ++c) a[i][c] = fmaf(-f[i], a[c][j], a[i][c]);
-      rhs[i] = fmaf(-f[i], rhs[j], rhs[i]);
-    }
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; --k) {
-    const float x = rhs[k] * id[k];
-    dx[k] = x;
-#pragma unroll
-    for (int i = 0; i < k; ++i) rhs[i] = fmaf(-a[k][i], x, rhs[i]);
-  }
-  return bad;
-}
-
-__device__ __forceinline__ void ldl6_solve(const float* tw, float dx[6]) {
-  if (ldl6_solve<false>(tw, dx)) ldl6_solve<true>(tw, dx);  // a (near-)zero pivot: rare
-}
-
-// sin/cos of GN increment angles.  Increments are small, so the float Taylor series (exact to
-// float rounding for |a| <= 1/16: next term a^9/9! < 1e-16) avoids sincosf's range reduction
-// on the critical path; ONE test for the three angles keeps the common case straight-line (three
-// independent polynomial chains); larger angles take the libm path.
-__device__ __forceinline__ void taylor_sincos(float a, float* s, float* c) {
-  const float a2 = a * a;
-  *s = a * fmaf(a2, fmaf(a2, fmaf(a2, -1.0f / 5040.0f, 1.0f / 120.0f), -1.0f / 6.0f), 1.0f);
-  *c = fmaf(a2, fmaf(a2, fmaf(a2, fmaf(a2, 1.0f / 40320.0f, -1.0f / 720.0f), 1.0f / 24.0f), -0.5f), 1.0f);
-}
-
-// src/defs.h:100-136 v2tEuler's rotation: Rd = Rx(a)*Ry(b)*Rz(c) (float) of dx[3..5].
-// ONE_CMP: the range test as one compare, the unsigned maximum of the three |angle| bit patterns
-// against the bits of 0.0625 (positive floats order as their bits; a NaN's bits lie above every
-// finite value's, so it takes the libm path as it does with the three float compares), and the
-// Taylor path as the fall-through.  The same path for every input, so the same bits.
-template <bool ONE_CMP = false>
-__device__ __forceinline__ void update_rotation(const float dx[6], float Rd[3][3]) {
-  float sa, ca, sb, cb, sc, cc;
-  bool small;
-  if constexpr (ONE_CMP) {
-    const unsigned a = __float_as_uint(dx[3]) & 0x7fffffffu, b = __float_as_uint(dx[4]) & 0x7fffffffu,
-                   c = __float_as_uint(dx[5]) & 0x7fffffffu;
-    const unsigned ab = a > b ? a : b;
-    small = __builtin_expect((ab > c ? ab : c) <= 0x3d800000u, 1);  // 0x3d800000: 0.0625f
-  } else {
-    small = fabsf(dx[3]) <= 0.0625f && fabsf(dx[4]) <= 0.0625f && fabsf(dx[5]) <= 0.0625f;
-  }
-  if (small) {
-    taylor_sincos(dx[3], &sa, &ca);
-    taylor_sincos(dx[4], &sb, &cb);
-    taylor_sincos(dx[5], &sc, &cc);
-  } else {
-    sincosf(dx[3], &sa, &ca);
-    sincosf(dx[4], &sb, &cb);
-    sincosf(dx[5], &sc, &cc);
-  }
-  // Rd = Rx(a)*Ry(b)*Rz(c) in closed form: the same products and sums as the 3x3 products
-  // of src/defs.h:133 with their structural zeros and ones folded away (x*1 = x, x+0 = x).
-  const float sasb = sa * sb, casb = ca * sb;
-  Rd[0][0] = cb * cc;
-  Rd[0][1] = -(cb * sc);
-  Rd[0][2] = sb;
-  Rd[1][0] = sasb * cc + ca * sc;
-  Rd[1][1] = ca * cc - sasb * sc;
-  Rd[1][2] = -(sa * cb);
-  Rd[2][0] = sa * sc - casb * cc;
-  Rd[2][1] = casb * sc + sa * cc;
-  Rd[2][2] = ca * cb;
-}
-
-// src/defs.h:100-136 v2tEuler: R = Rx(a)*Ry(b)*Rz(c) (float), t = v[0:3]; then
-// src/picp_solver.cpp:103 T <- v2tEuler(dx) * T.
-__device__ __forceinline__ void apply_update(const float dx[6], float R[9], float t[3]) {
-  // (round 4 pinned the contractions here with fp contract(off) for a fused append that is gone;
-  // it cost C2/C3 1-2 % -- profiles/r05/ab_regress/ -- and parity does not depend on it)
-  float Rd[3][3];
-  update_rotation(dx, Rd);
-  float Rn[9], tn[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float s = Rd[i][0] * R[j * 3 + 0];
-      s = s + Rd[i][1] * R[j * 3 + 1];
-      s = s + Rd[i][2] * R[j * 3 + 2];
-      Rn[j * 3 + i] = s;
-    }
-    float s = Rd[i][0] * t[0];
-    s = s + Rd[i][1] * t[1];
-    s = s + Rd[i][2] * t[2];
-    tn[i] = s + dx[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = tn[i];
-}
-
-// The 32 block-partial totals (double) -> the float words finish_round_f consumes, one word per
-// total so lane e of a wave can convert total e: H entries with the damping added on the
-// diagonal (src/picp_solver.cpp:96), -b, chi_in, chi_out as float, n_in and n_proj as int bits.
-__device__ __forceinline__ float total_word(const PicpArgs& A, int e, double t) {
-  const bool diag = (e == 0) | (e == 6) | (e == 11) | (e == 15) | (e == 18) | (e == 20);
-  // straight-line selects (lane e converts total e: branches would serialise the wave)
-  const double h = t + (diag ? (double)A.damping : 0.0);
-  const double d = (e < PICP_P_B) ? h : ((e < PICP_P_CHI_IN) ? -t : t);
-  const float f = (float)d;
-  const float c = __int_as_float((int32_t)t);
-  return (e < PICP_P_N_IN) ? f : ((e < 31) ? c : 0.0f);
-}
-
-// total_word for a lane that converts the same total e every round (the finishing wave of the
-// persistent and block kernels): what depends on e only, computed once per launch (the
-// persistent kernel keeps it in VGPRs, the block kernel in LDS), so the round pays one add, the
-// two converts and four bit operations instead of the classification of e (compares, lane masks
-// in SGPR pairs).  20 bytes, 24 with the double's alignment.
-//   add   : (double)damping on the diagonal of H, +0.0 on the rest of H (total_word's t + 0.0),
-//           -0.0 elsewhere (t + -0.0 is t for every t, -0.0 included)
-//   sign  : the sign bit for -b.  Negating the float after the conversion gives the bits of
-//           converting -t: round-to-nearest is symmetric
-//   fmask / imask : all ones where the word is the float / the int conversion (both zero: word 31)
-struct TotalLane {
-  double add;
-  unsigned sign, fmask, imask;
-};
-
-__device__ __forceinline__ TotalLane total_lane(const PicpArgs& A, int e) {
-  const bool diag = (e == 0) | (e == 6) | (e == 11) | (e == 15) | (e == 18) | (e == 20);
-  TotalLane k;
-  k.add = diag ? (double)A.damping : ((e < PICP_P_B) ? 0.0 : -0.0);
-  k.sign = (e >= PICP_P_B && e < PICP_P_CHI_IN) ? 0x80000000u : 0u;
-  k.fmask = (e < PICP_P_N_IN) ? ~0u : 0u;
-  k.imask = (e >= PICP_P_N_IN && e < 31) ? ~0u : 0u;
-  // opaque from here: as plain selects of e the compiler turns the masks back into compares whose
-  // lane masks it hoists into (spilled) SGPR pairs
-  asm volatile("" : "+v"(k.add), "+v"(k.sign), "+v"(k.fmask), "+v"(k.imask));
-  return k;
-}
-
-__device__ __forceinline__ float total_word(const TotalLane& k, double t) {
-  const unsigned f = __float_as_uint((float)(t + k.add)) ^ k.sign;
-  const unsigned c = (unsigned)(int32_t)t;
-  return __uint_as_float((f & k.fmask) | (c & k.imask));
-}
-
-// What a round leaves besides the pose: the state fields no later round reads.
-struct RoundOut {
-  float chi_in, chi_out;
-  int32_t n_in, n_proj, ok, done, converged;
-};
-
-// Finish round j of a problem from its converted totals (total_word: damping already in): the
-// min-inlier check, the 6x6 solve, the update and the icp_test loop rule.  The loop state a round
-// reads -- the pose R (column-major) / t and chi_prev -- is carried in registers by the finishing
-// wave (every lane computes the same values; no LDS state round trip on the critical path).
-// tw may be LDS.  (The elimination spread over a 16-lane row of the finishing wave was not
-// faster: DESIGN.md Appendix A, "DPP-row solve".)
-__device__ __forceinline__ void finish_round_pose(const PicpArgs& A, const float* tw, int j, float R[9],
-                                                  float t[3], float& chi_prev, RoundOut& o) {
-  o.chi_in = tw[PICP_P_CHI_IN];
-  o.chi_out = tw[PICP_P_CHI_OUT];
-  o.n_in = __float_as_int(tw[PICP_P_N_IN]);
-  o.n_proj = __float_as_int(tw[PICP_P_N_PROJ]);
-  o.converged = 0;  // a converged loop is done: no round runs after it
-  if (o.n_in < A.min_inliers) {  // src/picp_solver.cpp:97-100
-    o.ok = 0;
-    o.done = 1;
-    return;
-  }
-  float dx[6];
-  ldl6_solve(tw, dx);  // :96 (damping folded in by total_word), :102
-  apply_update(dx, R, t);  // :103
-  o.ok = 1;
-  o.done = 0;
-  // exec/icp_test.cpp:99-106
-  const float prev = chi_prev, cur = o.chi_in;
-  const float rel = (prev > 1e-10f) ? fabsf(prev - cur) / prev : 0.0f;
-  if (rel < A.conv_eps) {
-    o.converged = 1;
-    o.done = 1;
-  } else {
-    chi_prev = cur;
-  }
-  if (j >= A.max_rounds) o.done = 1;
-}
-
-// ---- the finish with the pose update spread over the lanes of the finishing wave ----
-// Only word l of the new pose is needed in lane l (the publish and the control row are "lane l
-// owns word l"), so after the uniform solve and rotation lane l < 12 computes word l alone instead
-// of every lane computing all twelve.  With i = l % 3 and base = 3 (l / 3), words 0-8 being R
-// column-major and 9-11 t, word l is row i of Rd times old[base .. base+2], plus dx[i] for t:
-// one formula for both.  FinishLanes holds what depends on the lane only, made once per launch:
-// the row masks (all ones where l % 3 == i, l < 12), the t mask (9 <= l < 12) and the word-12
-// mask, as opaque VGPR values (as TotalLane: plain selects of the lane become compares whose lane
-// masks are hoisted into SGPR pairs and spilled), and the LDS word index of old[0].
-struct FinishLanes {
-  unsigned row[3], tmask, m12;
-  int base;
-};
-
-__device__ __forceinline__ FinishLanes finish_lanes(int lane) {
-  FinishLanes k;
-  const bool pose = lane < 12;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) k.row[i] = (pose && lane % 3 == i) ? ~0u : 0u;
-  k.tmask = (lane >= 9 && lane < 12) ? ~0u : 0u;
-  k.m12 = (lane == 12) ? ~0u : 0u;
-  k.base = pose ? 3 * (lane / 3) : 0;
-  asm volatile("" : "+v"(k.row[0]), "+v"(k.row[1]), "+v"(k.row[2]), "+v"(k.tmask), "+v"(k.m12), "+v"(k.base));
-  return k;
-}
-
-__device__ __forceinline__ float lanes_pick(const FinishLanes& k, float a0, float a1, float a2) {
-  return __uint_as_float((__float_as_uint(a0) & k.row[0]) | (__float_as_uint(a1) & k.row[1]) |
-                         (__float_as_uint(a2) & k.row[2]));
-}
-
-// finish_round_pose for a whole wave: the same RoundOut and chi_prev in every lane, and the
-// return value is word l of the new pose in lane l < 12 (unspecified in the other lanes).  pose:
-// the twelve words of the old pose (LDS or global), read per lane before the solve.  The
-// convergence quotient (an IEEE division that feeds only the done word) is computed ahead of the
-// solve, unconditionally: prev <= 1e-10 selects 0 whatever the quotient is, so the same bits as
-// the branch of finish_round_pose.
-// The three products of a word are summed as apply_update's are where the pose is live in
-// registers (the round kernel, the persistent kernel with one item per lane), a contraction that
-// was the compiler's choice and is not the same for every row of Rd: rows 1 and 2 are
-// fma(Rdi2, o2, fma(Rdi0, o0, Rdi1 * o1)), and row 0, whose Rd01 is a negated product, is
-// fma(Rd02, o2, fma(Rd01, o1, Rd00 * o0)); t adds dx separately.  Here it is written out (fp
-// contract off) and no longer rests on the compiler: each lane multiplies its "first" pair, then
-// fuses the "second" and the third.  (Where the pose is re-read from LDS, the persistent kernel
-// with two or more items per lane, the compiler sums row 0 as the other rows; those kernels keep
-// the uniform form and their bits.)  t's add is selected, not masked to an add of zero, which
-// would turn a -0 word of R into +0.
-__device__ __forceinline__ float finish_round_lanes(const PicpArgs& A, const float* tw, const float* pose, int j,
-                                                    const FinishLanes& k, float& chi_prev, RoundOut& o) {
-#pragma clang fp contract(off)
-  const float old0 = pose[k.base], old1 = pose[k.base + 1], old2 = pose[k.base + 2];
-  o.chi_in = tw[PICP_P_CHI_IN];
-  o.chi_out = tw[PICP_P_CHI_OUT];
-  o.n_in = __float_as_int(tw[PICP_P_N_IN]);
-  o.n_proj = __float_as_int(tw[PICP_P_N_PROJ]);
-  o.converged = 0;
-  if (o.n_in < A.min_inliers) {  // the pose stays: lane l's own old word
-    o.ok = 0;
-    o.done = 1;
-    return lanes_pick(k, old0, old1, old2);
-  }
-  // exec/icp_test.cpp:99-106, the quotient first
-  const float prev = chi_prev, cur = o.chi_in;
-  float quot = fabsf(prev - cur) / prev;
-  asm volatile("" : "+v"(quot));  // computed here, not sunk under a branch behind the solve
-  const float rel = (prev > 1e-10f) ? quot : 0.0f;
-  const bool conv = rel < A.conv_eps;
-  float dx[6];
-  ldl6_solve(tw, dx);
-  float Rd[3][3];
-  update_rotation<true>(dx, Rd);
-  // rows 1, 2: (Rdi1, old1) first, (Rdi0, old0) second; row 0 the other way round
-  const unsigned u0 = __float_as_uint(old0), u1 = __float_as_uint(old1), r0 = k.row[0];
-  const float of = __uint_as_float((u0 & r0) | (u1 & ~r0)), os = __uint_as_float((u1 & r0) | (u0 & ~r0));
-  float s = lanes_pick(k, Rd[0][0], Rd[1][1], Rd[2][1]) * of;
-  s = fmaf(lanes_pick(k, Rd[0][1], Rd[1][0], Rd[2][0]), os, s);
-  s = fmaf(lanes_pick(k, Rd[0][2], Rd[1][2], Rd[2][2]), old2, s);
-  // t: dx + s with dx as the first operand, as the uniform form compiles: where both are NaN the
-  // add returns the first one's sign, and the compiler commutes a plain + (inline assembly: the
-  // operand order is part of the result here)
-  float st;
-  asm("v_add_f32_e32 %0, %1, %2" : "=v"(st) : "v"(lanes_pick(k, dx[0], dx[1], dx[2])), "v"(s));
-  const float w = __uint_as_float((__float_as_uint(st) & k.tmask) | (__float_as_uint(s) & ~k.tmask));
-  o.ok = 1;
-  o.converged = conv ? 1 : 0;
-  o.done = (conv || j >= A.max_rounds) ? 1 : 0;
-  chi_prev = conv ? prev : cur;
-  return w;
-}
-
-// The 128-byte state after round j, written field by field (padding zeroed): a whole-struct copy
-// from a local goes through a scratch alloca (SROA cannot split the memcpy).  dst: LDS or global.
-// store_state_rest: everything but the pose (finish_round_lanes has the pose one word per lane).
-template <typename S>
-__device__ __forceinline__ void store_state_rest(S* dst, float chi_prev, const RoundOut& o, int j) {
-  dst->chi_prev = chi_prev;
-  dst->chi_in = o.chi_in;
-  dst->chi_out = o.chi_out;
-  dst->n_in = o.n_in;
-  dst->n_proj = o.n_proj;
-  dst->rounds = j;
-  dst->done = o.done;
-  dst->ok = o.ok;
-  dst->converged = o.converged;
-#pragma unroll
-  for (int i = 0; i < 11; ++i) dst->pad[i] = 0;
-}
-
-template <typename S>
-__device__ __forceinline__ void store_state(S* dst, const float R[9], const float t[3], float chi_prev,
-                                            const RoundOut& o, int j) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) dst->R[i] = R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) dst->t[i] = t[i];
-  store_state_rest(dst, chi_prev, o, j);
-}
-
-// finish_round_pose on a stored state (the multi-launch round kernel: one lane).
-__device__ __forceinline__ void finish_round_f(const PicpArgs& A, const PicpState& s,
-                                               const float* tw, int j, PicpState& ns) {
-  float R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = s.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = s.t[i];
-  float chi_prev = s.chi_prev;
-  RoundOut o;
-  finish_round_pose(A, tw, j, R, t, chi_prev, o);
-  store_state(&ns, R, t, chi_prev, o, j);
-}
-
-// Finish round (j-1) of a problem from its block-partial totals (double): H, b, stats -> new
-// state.  One lane.
-__device__ __forceinline__ void finish_round(const PicpArgs& A, const PicpState& s,
-                                             const double* tot, int j, PicpState& ns) {
-  float tw[PICP_NPART];
-#pragma unroll
-  for (int e = 0; e < PICP_NPART; ++e) tw[e] = total_word(A, e, tot[e]);
-  finish_round_f(A, s, tw, j, ns);
-}
-
-
-// Refined hardware reciprocal and reciprocal square root in double: the v_rcp_f64 / v_rsq_f64
-// estimate and two Newton steps (full double precision), half the dependency chain of the IEEE
-// division / sqrt sequences.
-__device__ __forceinline__ double tri_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-__device__ __forceinline__ double tri_rsq(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = fma(0.5 * y, fma(-x * y, y, 1.0), y);
-  return fma(0.5 * y, fma(-x * y, y, 1.0), y);
-}
-
-// Right singular vector of the smallest singular value of the 4x4 DLT system A, by one-sided
-// (Hestenes) Jacobi, at most 10 sweeps, stopping after the first sweep that rotates nothing
-// (every later sweep would be a no-op); all indices compile-time so A and V stay in registers.
-// A is consumed.
-// A with a non-finite entry gives four NaNs.  Left alone it would give a finite vector: a column
-// with a NaN or Inf entry keeps one through every rotation (c x - s y of a non-finite x is
-// non-finite), its products gamma are NaN or Inf and fail the rotation test (NaN compares false,
-// Inf > Inf is false), its norm never compares below `best`, and so the result would be another
-// column of V, or column 0 of the identity when every column is affected (a NaN pixel: the finite
-// point (1, 0, 0)).  A finite A keeps finite norms (entries below 2^257), so the sum of the four
-// norms is finite exactly then.
-__device__ __forceinline__ void tri_null_jacobi(double A[4][4], double v[4]) {
-  double Vm[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) Vm[r][c] = (r == c) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 10; ++sweep) {
-    bool rotated = false;  // a sweep that rotates nothing leaves A and V unchanged: stop there
-#pragma unroll
-    for (int pq = 0; pq < 6; ++pq) {
-      const int p = (pq < 3) ? 0 : ((pq < 5) ? 1 : 2);
-      const int qq = (pq < 3) ? pq + 1 : ((pq < 5) ? pq - 1 : 3);
-      double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        alpha += A[k][p] * A[k][p];
-        beta += A[k][qq] * A[k][qq];
-        gamma += A[k][p] * A[k][qq];
-      }
-      // Rotate unless the pair is orthogonal to 1e-12 relative (gamma^2 <= 1e-24 alpha beta): the
-      // smaller rotations move the result below float precision.
-      if (fabs(gamma) > 1e-300 && gamma * gamma > 1e-24 * (alpha * beta)) {
-        rotated = true;
-        const double zeta = (beta - alpha) * tri_rcp(2.0 * gamma);
-        const double q = fma(zeta, zeta, 1.0);
-        const double t = ((zeta >= 0.0) ? 1.0 : -1.0) * tri_rcp(fabs(zeta) + q * tri_rsq(q));  // 1/(|z| + sqrt(1+z^2))
-        const double c = tri_rsq(fma(t, t, 1.0));
-        const double s = c * t;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double akp = A[k][p], akq = A[k][qq];
-          A[k][p] = c * akp - s * akq;
-          A[k][qq] = s * akp + c * akq;
-          const double vkp = Vm[k][p], vkq = Vm[k][qq];
-          Vm[k][p] = c * vkp - s * vkq;
-          Vm[k][qq] = s * vkp + c * vkq;
-        }
-      }
-    }
-    if (!rotated) break;  // identical result to running all 10 sweeps
-  }
-  double nrm[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) nrm[c] = A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c] + A[3][c] * A[3][c];
-  double best = nrm[0];
-  v[0] = Vm[0][0]; v[1] = Vm[1][0]; v[2] = Vm[2][0]; v[3] = Vm[3][0];
-#pragma unroll
-  for (int c = 1; c < 4; ++c) {
-    const bool take = nrm[c] < best;
-    best = take ? nrm[c] : best;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = take ? Vm[r][c] : v[r];
-  }
-  const bool finite = (nrm[0] + nrm[1]) + (nrm[2] + nrm[3]) <= DBL_MAX;  // false for NaN and Inf
-#pragma unroll
-  for (int r = 0; r < 4; ++r) v[r] = finite ? v[r] : __builtin_nan("");
-}
-
-// Two-view linear (DLT) triangulation of one point, cv::triangulatePoints as called from
-// src/cam.cpp:115 then convertPointsFromHomogeneous :118.  P1, P2: 3x4 ROW-major float.
-// A (4x4) in double; X_h = the right singular vector of A's smallest singular value, by the
-// one-sided Jacobi above (tri_null_jacobi).  (Inverse iteration on A^T A was slower: DESIGN.md
-// Appendix A, "inverse-iteration triangulation".)
-// A non-finite pixel or P entry gives (NaN, NaN, NaN), as OpenCV's SVD does (tri_null_jacobi's
-// rule: every input reaches an entry of A, a product of floats in double cannot overflow and
-// 0 * Inf is NaN, so A is finite exactly when the inputs are; a NaN W4 selects scale 1).
-__device__ inline void triangulate_dlt(const float* P1, const float* P2, float2 a, float2 b,
-                                       float out[3]) {
-  double A[4][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    A[0][k] = (double)a.x * (double)P1[8 + k] - (double)P1[0 + k];
-    A[1][k] = (double)a.y * (double)P1[8 + k] - (double)P1[4 + k];
-    A[2][k] = (double)b.x * (double)P2[8 + k] - (double)P2[0 + k];
-    A[3][k] = (double)b.y * (double)P2[8 + k] - (double)P2[4 + k];
-  }
-  double v[4];
-  tri_null_jacobi(A, v);
-  // points4D is float; convertPointsFromHomogeneous in float, scale 1 when |w| <= FLT_EPSILON
-  const float X4 = (float)v[0], Y4 = (float)v[1], Z4 = (float)v[2], W4 = (float)v[3];
-  const float scale = (fabsf(W4) > FLT_EPSILON) ? 1.0f / W4 : 1.0f;
-  out[0] = X4 * scale;
-  out[1] = Y4 * scale;
-  out[2] = Z4 * scale;
 }
 
 }  // namespace picp

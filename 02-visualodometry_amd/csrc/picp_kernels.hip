@@ -41,8 +41,13 @@ __device__ unsigned long long picp_stamps[2][PICP_STAMP_BLOCKS][8];
   } while (0)
 #endif
 
-#include "picp_device.h"
-
+#include "picp_item.h"
+#include "picp_pose.h"
+#include "picp_recip.h"
+#include "picp_solve6.h"
+#include "picp_triangulate.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -225,16 +230,9 @@ __global__ __launch_bounds__(PICP_BLOCK) void picp_round_kernel(
 
   // ---------------- linearize (src/picp_solver.cpp:56-91) ----------------
   Pose T;
-  T.r00 = s_in.R[0]; T.r10 = s_in.R[1]; T.r20 = s_in.R[2];
-  T.r01 = s_in.R[3]; T.r11 = s_in.R[4]; T.r21 = s_in.R[5];
-  T.r02 = s_in.R[6]; T.r12 = s_in.R[7]; T.r22 = s_in.R[8];
-  T.t0 = s_in.t[0]; T.t1 = s_in.t[1]; T.t2 = s_in.t[2];
+  pose_load(s_in.R, s_in.t, T);
   Cam C;
-  C.k00 = A.K[0]; C.k10 = A.K[1]; C.k20 = A.K[2];
-  C.k01 = A.K[3]; C.k11 = A.K[4]; C.k21 = A.K[5];
-  C.k02 = A.K[6]; C.k12 = A.K[7]; C.k22 = A.K[8];
-  C.maxx = A.maxx;
-  C.maxy = A.maxy;
+  cam_load(A.K, A.maxx, A.maxy, C);
   const float thr = A.threshold;
   const float inv_thr = 1.0f / thr;
   const bool keep = A.keep_outliers != 0;

@@ -11,7 +11,7 @@
 //   2. the problem's solver blocks (its first PICP_PSOLVERS blocks, one per XCD under round-robin
 //      placement) each sweep those granules until every tag matches, sum them in a FIXED order
 //      (deterministic: every solver gets the same bits), solve the damped 6x6 system and apply
-//      the update (picp_device.h: finish_round), then publish the new pose as 16 granules
+//      the update (picp_solve6.h: finish_round), then publish the new pose as 16 granules
 //      {round+1, word} twice: kept in their XCD's L2 and agent-scope;
 //   3. every other block polls its solver's 16 pose granules (one wave) -- the L2 copy once the
 //      first round has shown that it runs on the solver's XCD -- then starts the next round.
@@ -20,8 +20,12 @@
 // every spin is bounded by a per-round s_memrealtime deadline (timeout -> error word, loop exits), and
 // tags are offset by a per-problem round counter kept on the device (tagbase), so granules left
 // by earlier launches never match and no memset runs between launches.
-#include "picp_device.h"
+#include "picp_item.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_solve6.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -242,11 +246,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
   __syncthreads();
 
   Cam C;
-  C.k00 = A.K[0]; C.k10 = A.K[1]; C.k20 = A.K[2];
-  C.k01 = A.K[3]; C.k11 = A.K[4]; C.k21 = A.K[5];
-  C.k02 = A.K[6]; C.k12 = A.K[7]; C.k22 = A.K[8];
-  C.maxx = A.maxx;
-  C.maxy = A.maxy;
+  cam_load(A.K, A.maxx, A.maxy, C);
   const float thr = A.threshold;
   const float inv_thr = 1.0f / thr;
   const bool keep = A.keep_outliers != 0;
@@ -282,10 +282,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     PSTAMP(0);
     if (!solver) PSTAMP_W1(6);
     Pose T;
-    T.r00 = s_pose[0]; T.r10 = s_pose[1]; T.r20 = s_pose[2];
-    T.r01 = s_pose[3]; T.r11 = s_pose[4]; T.r21 = s_pose[5];
-    T.r02 = s_pose[6]; T.r12 = s_pose[7]; T.r22 = s_pose[8];
-    T.t0 = s_pose[9]; T.t1 = s_pose[10]; T.t2 = s_pose[11];
+    pose_load(s_pose, s_pose + 9, T);
     float v[PICP_NPART];
     Cnt nc = {0u, 0u};  // the wave's n_in / n_proj (scalar unit)
     if constexpr (NPT == 1) {  // one item per lane: the scalar path (latency-bound C2 frames)

@@ -1,7 +1,7 @@
 // picp_refine.hip -- structure-only Gauss-Newton: refine map points against all of their
 // observations with the poses held fixed (include/picp_c.h picp_refine_*).  The counterpart of the
 // PICP solve: the same projection, bounds test, chi2 gate and robust weight (classify_item,
-// picp_device.h, bit-identical to the solve kernels' decisions at the same point and pose), a 3x3
+// picp_item.h, bit-identical to the solve kernels' decisions at the same point and pose), a 3x3
 // damped system per point instead of a 6x6 per frame.
 //
 //   picp_refine_kernel : every round of every point in ONE launch.  A 16-lane DPP row owns a point
@@ -22,10 +22,13 @@
 // A row whose point has finished (or that has no point: n_points not a multiple of 16) keeps
 // running with an empty track, so EXEC is full at every DPP step; the wave leaves the round loop
 // when none of its rows is active.
-#include "picp_device.h"
-
 #include "picp_c.h"
+#include "picp_item.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_recip.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -33,43 +36,11 @@ using namespace picp;
 #define RF_ROW 16                      // lanes per point
 #define RF_PPB (RF_BLOCK / RF_ROW)     // points per block
 
-// dpp() of picp_device.h for a double: its two halves moved separately
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const long long q = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_mov_dpp((int)q, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(q >> 32), CTRL, 0xF, 0xF, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// v summed over the 16 lanes of a DPP row, the same bits in every lane: each step adds the partner
-// of an involution, so both partners form the same (commutative) sum.  EXEC must be full.
-__device__ __forceinline__ int row_sum(int v) {
-  v += __builtin_amdgcn_mov_dpp(v, DPP_ROW_MIRROR, 0xF, 0xF, true);
-  v += __builtin_amdgcn_mov_dpp(v, DPP_ROW_HALF_MIRROR, 0xF, 0xF, true);
-  v += __builtin_amdgcn_mov_dpp(v, DPP_QUAD_XOR2, 0xF, 0xF, true);
-  return v + __builtin_amdgcn_mov_dpp(v, DPP_QUAD_XOR1, 0xF, 0xF, true);
-}
-
-__device__ __forceinline__ double row_sum(double v) {
-  v += dpp64<DPP_ROW_MIRROR>(v);
-  v += dpp64<DPP_ROW_HALF_MIRROR>(v);
-  v += dpp64<DPP_QUAD_XOR2>(v);
-  return v + dpp64<DPP_QUAD_XOR1>(v);
-}
-
 // The sums of one linearisation of a point: the upper triangle of H, b, chi_in, chi_out, counts.
 struct RfAcc {
   double h00, h01, h02, h11, h12, h22, b0, b1, b2, chi_in, chi_out;
   int n_in, n_proj;
 };
-
-__device__ __forceinline__ void rf_load_pose(const RefinePose* __restrict__ poses, int k, Pose& T) {
-  const RefinePose P = poses[k];
-  T.r00 = P.r0.x; T.r01 = P.r0.y; T.r02 = P.r0.z; T.t0 = P.r0.w;
-  T.r10 = P.r1.x; T.r11 = P.r1.y; T.r12 = P.r1.z; T.t1 = P.r1.w;
-  T.r20 = P.r2.x; T.r21 = P.r2.y; T.r22 = P.r2.z; T.t2 = P.r2.w;
-}
 
 // One observation z of the point (X0, X1, X2) from pose T into the sums.  PH: the pinhole K
 // [fx 0 cx; 0 fy cy; 0 0 1] (is_pinhole): the terms K's zeros and its one make trivial are dropped.
@@ -102,7 +73,7 @@ __device__ __forceinline__ void refine_item(const Pose& T, const Cam& C, float t
     ph2 = (double)C.k20 * pc0 + (double)C.k21 * pc1 + (double)C.k22 * pc2;
   }
   // an unused observation (possibly with an infinite 1/z) contributes exact zeros
-  const double iz = use ? tri_rcp(ph2) : 0.0;
+  const double iz = use ? rcp_f64(ph2) : 0.0;
   const double ix = use ? ph0 * iz : 0.0, iy = use ? ph1 * iz : 0.0;
   const double e0 = use ? ix - (double)z.x : 0.0, e1 = use ? iy - (double)z.y : 0.0;
   // src/picp_solver.cpp:75-89: sqrt kernel weight, outliers only with keep
@@ -147,19 +118,19 @@ __device__ __forceinline__ void refine_item(const Pose& T, const Cam& C, float t
   A.b2 += W02 * e0 + W12 * e1;
 }
 
-// Damped 3x3 normal equations -> dx by LDL^T without pivoting, in double (pivot reciprocals: tri_rcp,
+// Damped 3x3 normal equations -> dx by LDL^T without pivoting, in double (pivot reciprocals: rcp_f64,
 // the hardware estimate and two Newton steps).  h: upper triangle
 // row-major (00 01 02 11 12 22) with the damping already on the diagonal; solves H dx = -b.
 // Returns false when H is not positive definite (a pivot <= 0 or NaN) or dx is not finite.
 __device__ __forceinline__ bool ldl3_solve(const double h[6], const double b[3], double dx[3]) {
   const double d0 = h[0];
-  const double i0 = tri_rcp(d0);
+  const double i0 = rcp_f64(d0);
   const double l10 = h[1] * i0, l20 = h[2] * i0;
   const double d1 = h[3] - l10 * h[1];
-  const double i1 = tri_rcp(d1);
+  const double i1 = rcp_f64(d1);
   const double l21 = (h[4] - l20 * h[1]) * i1;
   const double d2 = h[5] - l20 * h[2] - l21 * (l21 * d1);
-  const double i2 = tri_rcp(d2);
+  const double i2 = rcp_f64(d2);
   const double y0 = -b[0];
   const double y1 = -b[1] - l10 * y0;
   const double y2 = -b[2] - l20 * y0 - l21 * y1;
@@ -238,14 +209,6 @@ __device__ __forceinline__ void rf_store(const RfState& S, int64_t p, float* __r
   stats[p] = s;
 }
 
-__device__ __forceinline__ void rf_cam(const RefineArgs& a, Cam& C) {
-  C.k00 = a.K[0]; C.k10 = a.K[1]; C.k20 = a.K[2];
-  C.k01 = a.K[3]; C.k11 = a.K[4]; C.k21 = a.K[5];
-  C.k02 = a.K[6]; C.k12 = a.K[7]; C.k22 = a.K[8];
-  C.maxx = a.maxx;
-  C.maxy = a.maxy;
-}
-
 template <bool PH>
 __global__ __launch_bounds__(RF_BLOCK) void picp_refine_kernel(const RefineArgs a,
                                                               const RefinePose* __restrict__ poses,
@@ -258,7 +221,7 @@ __global__ __launch_bounds__(RF_BLOCK) void picp_refine_kernel(const RefineArgs 
   const int64_t p = (int64_t)blockIdx.x * RF_PPB + (threadIdx.x / RF_ROW);
   const bool has_point = p < a.n_points;
   Cam C;
-  rf_cam(a, C);
+  cam_load(a.K, a.maxx, a.maxy, C);
   const bool keep = a.keep_outliers != 0;
 
   int64_t o0 = 0;
@@ -280,7 +243,7 @@ __global__ __launch_bounds__(RF_BLOCK) void picp_refine_kernel(const RefineArgs 
     const int n = S.active ? len : 0;  // a finished row idles with an empty track
     for (int i = sub; i < n; i += RF_ROW) {
       Pose T;
-      rf_load_pose(poses, obs_pose[o0 + i], T);
+      pose_load(poses[obs_pose[o0 + i]], T);
       refine_item<PH>(T, C, a.threshold, keep, S.X0, S.X1, S.X2, obs_uv[o0 + i], A);
     }
     // all 64 lanes are here (no lane leaves the kernel early): EXEC is full for the DPP steps

@@ -62,12 +62,7 @@ extern "C" int picp_refine_set_poses(picp_refine_t* h, const float* T_wc, int n_
   HIP_TRY(hipSetDevice(h->device));
   // the 48-B table the kernel gathers from: the rows of [R | t] of every pose
   std::vector<RefinePose> tab((size_t)n_poses);
-  for (int k = 0; k < n_poses; ++k) {
-    const float* T = T_wc + 16 * (size_t)k;  // column-major 4x4
-    tab[k].r0 = make_float4(T[0], T[4], T[8], T[12]);
-    tab[k].r1 = make_float4(T[1], T[5], T[9], T[13]);
-    tab[k].r2 = make_float4(T[2], T[6], T[10], T[14]);
-  }
+  for (int k = 0; k < n_poses; ++k) tab[k] = picp::pose_to_rows(T_wc + 16 * (size_t)k);
   int rc = h->poses_d.grow(n_poses);
   if (!rc) rc = h->adj.T_d.grow(16 * (int64_t)n_poses);
   if (rc) return rc;

@@ -54,22 +54,8 @@ extern "C" int picp_device_count(int* n) {
 }
 
 // ------------------------------------------------------------------------------------
-// pose helpers (column-major 4x4 <-> state R(col-major 3x3), t)
+// state helpers (the pose conversions: picp_pose.h)
 // ------------------------------------------------------------------------------------
-void pose_to_state(const float T[16], PicpState& s) {
-  for (int j = 0; j < 3; ++j)
-    for (int i = 0; i < 3; ++i) s.R[j * 3 + i] = T[j * 4 + i];
-  for (int i = 0; i < 3; ++i) s.t[i] = T[12 + i];
-}
-
-void state_to_pose(const PicpState& s, float T[16]) {
-  memset(T, 0, 16 * sizeof(float));
-  for (int j = 0; j < 3; ++j)
-    for (int i = 0; i < 3; ++i) T[j * 4 + i] = s.R[j * 3 + i];
-  for (int i = 0; i < 3; ++i) T[12 + i] = s.t[i];
-  T[15] = 1.0f;
-}
-
 void state_to_stats(const PicpState& s, picp_stats& st) {
   st.chi_in = s.chi_in;
   st.chi_out = s.chi_out;

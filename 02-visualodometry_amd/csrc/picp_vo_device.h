@@ -1,8 +1,12 @@
 // picp_vo_device.h -- device pieces of the VO step shared by the VO kernels (picp_vo.hip) and the
-// PICP block kernel's fused VO gather (picp_block.hip): pose algebra, the ordered block
-// compaction and the append (exec/icp_test.cpp:113-132, src/my_utilities.cpp:413-434, src/cam.cpp:94-140).
+// PICP block kernel's fused VO gather (picp_block.hip): the ordered block compaction and the
+// append (exec/icp_test.cpp:113-132, src/my_utilities.cpp:413-434, src/cam.cpp:94-140).
 #pragma once
-#include "picp_device.h"
+#include <hip/hip_runtime.h>
+
+#include "picp_internal.h"
+#include "picp_pose.h"
+#include "picp_triangulate.h"
 
 namespace picp {
 
@@ -16,40 +20,6 @@ __device__ unsigned long long picp_voa_tstamp[5];
 #else
 #define VOA_TS(v) (void)0
 #endif
-
-// Eigen::Isometry3f::inverse() of a column-major 4x4 (oracle/picp_oracle.c or_iso_inverse order)
-__device__ __forceinline__ void vo_iso_inverse(const float* T, float* Ti) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Ti[j * 4 + i] = T[i * 4 + j];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    float s = Ti[0 * 4 + i] * T[12 + 0];
-    s = s + Ti[1 * 4 + i] * T[12 + 1];
-    s = s + Ti[2 * 4 + i] * T[12 + 2];
-    Ti[12 + i] = -s;
-  }
-  Ti[3] = Ti[7] = Ti[11] = 0.0f;
-  Ti[15] = 1.0f;
-}
-
-// P = K * inverse(T_cw)(0:3, 0:4), row-major 3x4 (src/cam.cpp:109-112)
-__device__ __forceinline__ void vo_projection(const float* K, const float* Tcw, float* P) {
-#pragma clang fp contract(off)
-  float Ti[16];
-  vo_iso_inverse(Tcw, Ti);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float s = K[0 * 3 + i] * Ti[j * 4 + 0];
-      s = s + K[1 * 3 + i] * Ti[j * 4 + 1];
-      s = s + K[2 * 3 + i] * Ti[j * 4 + 2];
-      P[i * 4 + j] = s;
-    }
-}
 
 // ordered block compaction: returns this lane's rank among the flagged lanes of the chunk;
 // *total = flagged lanes in the chunk.  Contains two barriers (all lanes must call).
@@ -111,7 +81,7 @@ __device__ __forceinline__ void vo_append_body(const VoArgs& a, int t, int s, co
 #pragma unroll
       for (int k = 0; k < 16; ++k) Tp[k] = a.poses[16 * (G.slot0 + t) + k];
       const PicpState st = *st_res;
-      float Twc[16];
+      float Twc[16];  // (state_to_pose written out: with the helper the append kernel's code changes)
 #pragma unroll
       for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -278,12 +248,7 @@ __device__ __forceinline__ void vo_append_body(const VoArgs& a, int t, int s, co
     float Twc[16];
     vo_iso_inverse(sTn, Twc);
     PicpState st = {};
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) st.R[j * 3 + i] = Twc[j * 4 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) st.t[i] = Twc[12 + i];
+    pose_to_state(Twc, st);
     a.st_in[s] = st;
 #ifdef VOA_TSTAMP
     VOA_TS(vt4);

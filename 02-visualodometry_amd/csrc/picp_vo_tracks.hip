@@ -21,8 +21,9 @@
 //                            refiner's [R | t] rows.
 #include <algorithm>
 
-#include "picp_vo_device.h"
 #include "picp_launch.h"
+#include "picp_pose.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
@@ -83,26 +84,13 @@ __global__ __launch_bounds__(VT_SCAN) void vo_tracks_scan_kernel(const VoTrackCs
   const int s = (int)blockIdx.x;
   const int64_t pb = B.pt_base[s], n = B.pt_base[s + 1] - pb;
   __shared__ int s_w[VT_SCAN_WAVES];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int64_t carry = 0;
   for (int64_t c0 = 0; c0 < n; c0 += VT_SCAN) {  // uniform
     const int64_t j = c0 + threadIdx.x;
     const int v = j < n ? B.cnt[pb + j] + 2 : 0;  // the matches, x and y
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d *= 2) {
-      const int y = __shfl_up(x, d);
-      x += lane >= d ? y : 0;
-    }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < VT_SCAN_WAVES; ++k) {
-      pre += (k < w) ? s_w[k] : 0;
-      tot += s_w[k];
-    }
-    if (j < n) B.rel[pb + j] = carry + pre + x - v;
+    int tot;
+    const int excl = block_scan<VT_SCAN_WAVES>(v, s_w, &tot);
+    if (j < n) B.rel[pb + j] = carry + excl;
     carry += tot;
     __syncthreads();  // s_w is reused by the next chunk
   }
@@ -178,11 +166,7 @@ __global__ __launch_bounds__(VT_BLOCK) void vo_tracks_pose_kernel(const VoTrackC
   vo_iso_inverse(T, Ti);
 #pragma unroll
   for (int q = 0; q < 16; ++q) B.pose_wc[16 * k + q] = Ti[q];
-  RefinePose P;  // the rows of [R | t] (picp_refine_set_poses)
-  P.r0 = make_float4(Ti[0], Ti[4], Ti[8], Ti[12]);
-  P.r1 = make_float4(Ti[1], Ti[5], Ti[9], Ti[13]);
-  P.r2 = make_float4(Ti[2], Ti[6], Ti[10], Ti[14]);
-  B.rposes[k] = P;
+  B.rposes[k] = pose_to_rows(Ti);  // as picp_refine_set_poses
 }
 
 extern "C" hipError_t picp_launch_vo_tracklog(hipStream_t stream, const VoArgs* a, int t, const VoTrackLog* L) {

@@ -1078,7 +1078,7 @@ def refine_points(K, rows, cols, poses, track_off, obs_pose, obs_uv, xyz, device
 
 def selftest_rcp(e_lo=-8, e_hi=8, device=0):
     """Floats (both signs, exponents [e_lo, e_hi)) where the kernels' fast reciprocal differs
-    from the IEEE division; 0 proves it for every |x| in [2^-100, 2^100] (picp_device.h)."""
+    from the IEEE division; 0 proves it for every |x| in [2^-100, 2^100] (picp_recip.h)."""
     n = ctypes.c_uint64()
     _check(lib().picp_selftest_rcp(device, e_lo, e_hi, ctypes.byref(n)))
     return n.value

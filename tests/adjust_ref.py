@@ -188,11 +188,30 @@ def tiny_case(K, rows=480, cols=640):
     return {**C, "poses": poses, "off": off, "obs_pose": obs_pose, "obs_uv": obs_uv, "fixed": np.zeros(3, bool)}
 
 
+def many_poses_case(n, K, rows=480, cols=640, seed=8):
+    """n identity poses (the view build does not read them) and n // 2 + 2 points: point i is tracked
+    by poses i and (7 i + 3) mod n and, every 64th point, by pose n - 1.  The poses from 0 up to the
+    number of points are a run of non-empty lists (past one scan chunk of 1,024 poses for n = 2049),
+    the rest are hit or not by the second rule, and the last pose's list is long."""
+    m = n // 2 + 2
+    rng = np.random.default_rng(seed)
+    tracks = [[i, (7 * i + 3) % n] + ([n - 1] if i % 64 == 0 else []) for i in range(m)]
+    off = np.zeros(m + 1, np.int64)
+    off[1:] = np.cumsum([len(t) for t in tracks])
+    obs_pose = np.concatenate(tracks).astype(np.int32)
+    obs_uv = rng.uniform(5.0, min(rows, cols) - 6.0, (len(obs_pose), 2)).astype(np.float32)
+    lens = np.bincount(obs_pose, minlength=n)
+    assert (lens == 0).any() and lens[n - 1] > 8 and (lens[:m] > 0).all(), (n, lens.max())
+    return {"K": np.asarray(K, np.float32), "rows": rows, "cols": cols,
+            "poses": np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)), "off": off, "obs_pose": obs_pose,
+            "obs_uv": obs_uv, "start": np.zeros((m, 3), np.float32), "fixed": np.zeros(n, bool)}
+
+
 _cache = {}
 
 
 def case(oracle, name):
-    """data_perturbed | synth | two_long_<n> | tiny"""
+    """data_perturbed | synth | two_long_<n> | tiny | many_poses_<n>"""
     if name in _cache:
         return _cache[name]
     K = RO._vo().K
@@ -214,6 +233,8 @@ def case(oracle, name):
         C["poses"][0] = oracle.v2t_euler(d).astype(np.float64) @ C["truth_poses"][0].astype(np.float64)
     elif name == "tiny":
         C = tiny_case(K)
+    elif name.startswith("many_poses_"):
+        C = many_poses_case(int(name.split("_")[2]), K)
     else:
         raise KeyError(name)
     _cache[name] = C

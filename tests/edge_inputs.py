@@ -72,7 +72,7 @@ def nearby(T, seed):
 
 
 def depth_f32(T, x, y, z):
-    """item_depth of picp_device.h in float32: row 2 of R p + t, left to right, every operation
+    """item_depth of picp_item.h in float32: row 2 of R p + t, left to right, every operation
     rounded on its own (no contraction)."""
     T = np.asarray(T, f32)
     x, y, z = f32(x), f32(y), f32(z)

@@ -88,6 +88,22 @@ def test_shipped_device_code_has_no_packed_fp32_and_no_calls():
     assert not bad, bad
 
 
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"), reason="no llvm-objdump")
+def test_code_object_compare_of_the_library_with_itself():
+    """tools/codeobj.py --compare: the shipped library against itself pairs every code object,
+    reports each identical, and sees the function symbols the census sees."""
+    import io
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import codeobj
+    import picp_amd
+    out = io.StringIO()
+    ok, seen = codeobj.compare(picp_amd.LIB_PATH, picp_amd.LIB_PATH, out=out)
+    lines = out.getvalue().splitlines()
+    assert ok and len(lines) >= 10 and all(": identical (" in l for l in lines), out.getvalue()
+    assert len(seen) == len(codeobj.census(picp_amd.LIB_PATH))
+
+
 def test_null_arguments_are_rejected_without_device():
     import picp_amd
     L = picp_amd.lib()

@@ -74,6 +74,9 @@ def _assert_view(r, C, what):
 def test_view_is_exact(native, oracle):
     names = ["data_perturbed", "synth", "tiny"] + _two_long_names(native)
     assert names[-1] == "two_long_2049"  # the cases below were sized for a tile of 1024
+    # the scan of the per-pose counts runs in chunks of 1,024 poses: one chunk short of full, full,
+    # one pose into the second chunk, and three chunks with the boundary inside the non-empty run
+    names += ["many_poses_%d" % n for n in (1023, 1024, 1025, 2049)]
     for name in names:
         C = AR.case(oracle, name)
         r = _refiner(native, C)

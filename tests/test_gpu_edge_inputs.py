@@ -1,7 +1,7 @@
 """GPU tests of the solve, classify and refine kernels on extreme and NaN inputs
 (tests/edge_inputs.py; the oracle's half of every statement is tests/test_edge_inputs_cpu.py).
 
-The per-correspondence code of picp_device.h has four wave-level branches that depend on the
+The per-correspondence code of picp_item.h has four wave-level branches that depend on the
 VALUES of the data.  The cases below take each of them the rare way:
 
   1. The reciprocal of the depth: accumulate_pinhole2 (RCP_CHECK), accumulate_regs,

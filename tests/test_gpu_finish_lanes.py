@@ -1,4 +1,4 @@
-"""The lane-parallel finish of a round (picp_device.h finish_round_lanes, the persistent kernel's)
+"""The lane-parallel finish of a round (picp_solve6.h finish_round_lanes, the persistent kernel's)
 against the uniform one (finish_round_pose, the graph path's round kernel): the same bits.
 
 picp_selftest_finish runs both forms on the same totals, pose and loop state in one launch, one

@@ -411,7 +411,7 @@ def _batch_mode(native, sizes, mode, **kw):
 def test_persistent_and_graph_modes_agree_with_oracle(native, oracle, n, of, keep, conv):
     """Single-launch persistent solve vs one-launch-per-round graph solve vs the oracle.  The
     sizes cover every register-resident shape: 1 item per lane (100k), 2 (250k) and 4 (500k) --
-    the one-slot accumulation -- and 8 (1M) -- the pair form (picp_device.h acc_pairs)."""
+    the one-slot accumulation -- and 8 (1M) -- the pair form (picp_item.h acc_pairs)."""
     synth = _synth()
     p = synth.make_problem(n, seed=77, outlier_frac=of, pixel_noise=0.5, shuffle=False)
     res = {}

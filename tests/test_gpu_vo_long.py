@@ -48,7 +48,7 @@ POSE_TOL = 1e-4
 
 def _iso_inverse_f32(T):
     """Eigen::Isometry3f::inverse() of a camera-in-world pose in float32, in the order the GPU's
-    append computes the next step's prior (picp_vo_device.h vo_iso_inverse, contraction off):
+    append computes the next step's prior (picp_pose.h vo_iso_inverse, contraction off):
     R^T, and -(R^T t) summed k = 0, 1, 2 with every product and sum rounded to float32."""
     R = np.asarray(T, np.float32)[:3, :3]
     t = np.asarray(T, np.float32)[:3, 3]

@@ -201,6 +201,11 @@ def test_tracks_equal_the_reference(native, oracle, name):
             if s_last == 0:
                 acc0, bi0 = refs[0]["wm"][f - 1]
                 np.testing.assert_array_equal(left, np.where(acc0, bi0, -1))
+    if name == "tails_seg":
+        # the scan of the track lengths runs per segment in chunks of 1,024 points: among the named
+        # cases this one has a segment of more than two chunks and one of less than a chunk
+        n_map = [len(out["map"][k][0]) for k in range(len(C["first"]))]
+        assert max(n_map) > 2048 and min(n_map) < 1024, n_map
     total = 0
     for k in range(len(C["first"])):
         _assert_tracks_equal(out["tracks"][k], refs[k], "%s segment %d" % (name, k))

@@ -26,7 +26,10 @@
 #include <cstdlib>
 #include <vector>
 
-#include "picp_device.h"
+#include "picp_item.h"
+#include "picp_pose.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 using namespace picp;
 
 #define FMA_ASM(a, b, c) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(a) : "v"(b), "v"(c))

@@ -12,7 +12,10 @@
 #include <cstdlib>
 #include <vector>
 
-#include "picp_device.h"
+#include "picp_item.h"
+#include "picp_pose.h"
+#include "picp_variant.h"
+#include "picp_wave.h"
 using namespace picp;
 
 template <int NPT, bool PAIRS, int BS>

@@ -1,7 +1,7 @@
 // Microbenchmark (diagnostic, not shipped): cycles of the pieces of finish_round_f on one wave.
 #include <cstdio>
 #include <vector>
-#include "picp_device.h"
+#include "picp_solve6.h"
 using namespace picp;
 
 // ---- experimental finish variants (round 3); not in the product ----

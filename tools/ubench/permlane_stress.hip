@@ -6,7 +6,7 @@
 //
 //   victim 0: 16 v_permlane32_swap + 8 v_permlane16_swap (the reduction's pattern), every result
 //             compared with the value the swap must deliver (integer data)
-//   victim 1: wave_reduce32 (swap form, picp_device.h) vs wave_reduce32_bperm on the same floats
+//   victim 1: wave_reduce32 (swap form, picp_wave.h) vs wave_reduce32_bperm on the same floats
 //   victim 2: the DPP row stages alone (row_mirror / row_half_mirror / quad_perm), vs ds_bpermute
 //   victim 3: transcendental results: v_rcp_f32 / v_rsq_f32 of hashed operands (a new operand every
 //             instruction) consumed by FMAs, each checked by its residual (|x*r - 1| <= 2^-21)
@@ -24,7 +24,7 @@
 //             chain whose every v_rcp_f32 is followed by 16 wait states (inline asm); mismatches
 //             counted for lanes 0-47 in the low half of the counter and lanes 48-63 times 2^32
 //   victim 8: the same with v_sqrt_f32 / v_rsq_f32 / v_exp_f32 / v_log_f32 producers
-//   victim 9: apply_update (picp_device.h: Rx*Ry*Rz compose, packed-FP32 code) on inputs that are
+//   victim 9: apply_update (picp_solve6.h: Rx*Ry*Rz compose, packed-FP32 code) on inputs that are
 //             the same in every lane: every lane must get lane 0's bits (lanes 0-47 / 48-63 counted
 //             as in victim 7); victim 10: the same chain of packed FMAs (v_pk_fma_f32) alone
 //   victims 11-16: one packed-FP32 instruction form each (inline asm, dependent chains, inputs the
@@ -47,7 +47,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "picp_device.h"
+#include "picp_solve6.h"
+#include "picp_wave.h"
 
 using namespace picp;
 
