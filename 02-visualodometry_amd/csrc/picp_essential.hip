@@ -28,6 +28,7 @@
 
 #include "picp_internal.h"
 #include "picp_launch.h"
+#include "picp_poly.h"
 
 #pragma clang fp contract(off)
 
@@ -106,70 +107,6 @@ __device__ void umul(const double* a, int da, const double* b, int db, double* r
   for (int k = 0; k <= da + db; ++k) r[k] = 0.0;
   for (int i = 0; i <= da; ++i)
     for (int j = 0; j <= db; ++j) r[i + j] += a[i] * b[j];
-}
-
-__device__ double ueval(const double* a, int d, double z) {
-  double s = a[d];
-  for (int k = d - 1; k >= 0; --k) s = s * z + a[k];
-  return s;
-}
-
-// real roots (ascending) of a degree-d polynomial, d <= 10: bottom-up through the derivatives,
-// one bisection per monotone interval between consecutive critical points (oracle: real_roots)
-__device__ int real_roots(const double* p_in, int d, double* roots) {
-  double p[11];
-  for (int k = 0; k <= d; ++k) p[k] = p_in[k];
-  double amax = 0.0;
-  for (int k = 0; k <= d; ++k) amax = fmax(amax, fabs(p[k]));
-  if (amax == 0.0) return 0;
-  while (d > 0 && fabs(p[d]) <= 1e-14 * amax) --d;
-  if (d == 0) return 0;
-  double bound = 0.0;
-  for (int k = 0; k < d; ++k) bound = fmax(bound, fabs(p[k] / p[d]));
-  bound += 1.0;
-  double der[11][11];
-  for (int k = 0; k <= d; ++k) der[d][k] = p[k];
-  for (int deg = d - 1; deg >= 1; --deg)
-    for (int k = 0; k <= deg; ++k) der[deg][k] = der[deg + 1][k + 1] * (double)(k + 1);
-  double crit[11], cur[11];
-  int nc = 0, nr = 0;
-  for (int deg = 1; deg <= d; ++deg) {
-    double ends[12];
-    int ne = 0;
-    ends[ne++] = -bound;
-    for (int i = 0; i < nc; ++i) ends[ne++] = crit[i];
-    ends[ne++] = bound;
-    nr = 0;
-    for (int i = 0; i + 1 < ne; ++i) {
-      double lo = ends[i], hi = ends[i + 1];
-      double flo = ueval(der[deg], deg, lo), fhi = ueval(der[deg], deg, hi);
-      if (flo == 0.0) {
-        if (nr == 0 || cur[nr - 1] != lo) cur[nr++] = lo;
-        continue;
-      }
-      if ((flo < 0.0) == (fhi < 0.0)) continue;
-      for (int it = 0; it < 200 && hi - lo > 0.0; ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (mid <= lo || mid >= hi) break;
-        const double fm = ueval(der[deg], deg, mid);
-        if (fm == 0.0) {
-          lo = hi = mid;
-          break;
-        }
-        if ((fm < 0.0) == (flo < 0.0)) {
-          lo = mid;
-          flo = fm;
-        } else {
-          hi = mid;
-        }
-      }
-      cur[nr++] = 0.5 * (lo + hi);
-    }
-    for (int i = 0; i < nr; ++i) crit[i] = cur[i];
-    nc = nr;
-  }
-  for (int i = 0; i < nr; ++i) roots[i] = cur[i];
-  return nr;
 }
 
 // Nister's five-point solver (oracle: or_five_point): up to 10 unit-norm row-major E

@@ -13,6 +13,7 @@
 #include "picp_batch.h"
 #include "picp_host.h"
 #include "picp_launch.h"
+#include "picp_pnp_host.h"
 
 #define set_err picp_set_err
 
@@ -21,6 +22,8 @@ struct picp_handle {
   DevBuf<float> world_d, image_d;
   int64_t n_world = 0, n_image = 0;
   DevBuf<int2> pairs_d;
+  DevBuf<int64_t> pnp_offs;      // picp_relocalize: {0, m, the planes' offset}
+  PnpRun pnp;                    // picp_relocalize: its device buffers, kept between calls
   std::vector<int32_t> pairs_h;  // cached copy of the current correspondences
   int64_t m = -1;                // -1: none set
   bool have_points = false;
@@ -299,4 +302,32 @@ extern "C" int picp_classify(picp_t* h, float threshold, uint8_t* state, float* 
   int rc = handle_prepare(h);
   if (rc) return rc;
   return batch_classify(h->b, threshold, h->pose, state, chi2, proj_uv, nullptr, inlier_idx, counts);
+}
+
+// P3P RANSAC on the gathered planes (picp_pnp_host.h): problem 0 of a one-problem batch
+extern "C" int picp_relocalize(picp_t* h, const picp_pnp_params* prm, int32_t* inliers) {
+  CHECK_ARG(h, "picp_relocalize: null handle");
+  int rc = handle_prepare(h);
+  if (rc) return rc;
+  picp_batch* b = h->b;
+  PnpRun& R = h->pnp;
+  rc = pnp_args(&R.A, b->K, b->rows, b->cols, prm, 1);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(b->device));
+  const int64_t offs[3] = {0, h->m, h->m > 0 ? b->plane_off[0] : 0};
+  if ((rc = h->pnp_offs.grow(3))) return rc;
+  HIP_TRY(hipMemcpyAsync(h->pnp_offs, offs, sizeof(offs), hipMemcpyHostToDevice, b->stream));
+  R.I = PnpItems{b->X(), b->Y(), b->Z(), b->U(), b->V(), 1, 1, h->pnp_offs, h->pnp_offs + 2};
+  if ((rc = pnp_prepare(&R, b->stream, offs, false))) return rc;
+  HIP_TRY(pnp_enqueue(&R, b->stream, nullptr, 0));
+  float T[16];
+  int32_t n_in = 0, found = 0;
+  HIP_TRY(hipMemcpyAsync(T, R.T, sizeof(T), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(&n_in, R.inliers, sizeof(n_in), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(&found, R.found, sizeof(found), hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (inliers) *inliers = n_in;
+  if (!found) return PICP_TOO_FEW_INLIERS;
+  memcpy(h->pose, T, sizeof(h->pose));
+  return PICP_OK;
 }

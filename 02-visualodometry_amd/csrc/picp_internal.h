@@ -147,6 +147,35 @@ struct EssArgs {
 };
 
 // ---------------------------------------------------------------------------------------
+// absolute pose by P3P RANSAC (picp_pnp.hip), by value
+struct PnpArgs {
+  float K[9];            // camera matrix, column-major
+  float maxx, maxy;      // cols-1, rows-1
+  float threshold;       // chi2 gate (squared pixels)
+  int32_t pinhole;       // classify_item's camera path (set by the launcher)
+  double Kinv[9];        // K^-1, row-major (the back-projection of the three sampled pixels)
+  uint64_t seed;
+  int32_t n_problems;
+  int32_t hyp;           // hypotheses per problem
+  int32_t min_inliers;
+  int32_t prob0;         // batch position of problem 0 (the sampling function's problem index)
+};
+
+// The correspondences of a PnP batch, packed (xyz float3, uv float2: x = xyz, y = xyz + 1,
+// z = xyz + 2, sx = 3, ...) or as the planes of a picp_batch (strides 1).  Correspondence j of
+// problem i is element base[i] + j; offs (n_problems + 1) gives the sizes.
+struct PnpItems {
+  const float* x;
+  const float* y;
+  const float* z;
+  const float* u;
+  const float* v;
+  int32_t sx, su;        // element strides of x/y/z and of u/v
+  const int64_t* offs;
+  const int64_t* base;
+};
+
+// ---------------------------------------------------------------------------------------
 // device-resident VO sequence (picp_vo.hip; VoSegment: picp_problem.h)
 struct VoStep {     // per pose slot; slot 0 of a segment = the bootstrap
   int32_t n_corr;   // map correspondences of the frame (PICP input size)

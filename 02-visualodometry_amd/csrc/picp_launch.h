@@ -96,6 +96,22 @@ hipError_t picp_launch_essential(hipStream_t stream, const EssArgs* args, const 
                                  const float* p2, int32_t* idx, double* Es, int32_t* ns, int32_t* cnt,
                                  float* T_out, int32_t* inliers, int32_t* good, uint8_t* mask);
 
+// ---- picp_pnp.hip
+// Per-(problem, hypothesis) arrays are indexed p * hyp + h: samples 3, n_roots 1, hyp_T 4 poses of
+// 12 floats (R column-major, then t), cnt 4 (zeroed by the caller before the score launch).
+int picp_pnp_score_tile(void);  // correspondences one score block holds
+int picp_pnp_hyp_tile(void);    // hypotheses per count tile (a slice of the score grid's y takes whole tiles)
+hipError_t picp_launch_pnp_samples(hipStream_t stream, const PnpArgs* A, const PnpItems* I, int32_t* samples);
+hipError_t picp_launch_pnp_solve(hipStream_t stream, const PnpArgs* A, const PnpItems* I, const int32_t* samples,
+                                 int32_t* n_roots, float* hyp_T);
+// blk[nb]: (problem, first correspondence) of every score block; hsplit: hypothesis slices (grid y)
+hipError_t picp_launch_pnp_score(hipStream_t stream, const PnpArgs* A, const PnpItems* I, int nb, const int2* blk,
+                                 int hsplit, const int32_t* n_roots, const float* hyp_T, int32_t* cnt);
+// mask (nullable) is indexed offs[p] + j
+hipError_t picp_launch_pnp_select(hipStream_t stream, const PnpArgs* A, const PnpItems* I, const int32_t* n_roots,
+                                  const float* hyp_T, const int32_t* cnt, float* T_out, int32_t* inliers,
+                                  int32_t* found, uint8_t* mask);
+
 // ---- picp_match.hip
 hipError_t picp_launch_match(hipStream_t stream, int n_problems, int64_t max_nq, const float* q_desc,
                              const float* r_desc, const MatchProblem* probs, int dim, float dist_thr,

@@ -1,0 +1,401 @@
+// picp_pnp.hip -- absolute pose without a prior: P3P inside RANSAC for a ragged batch of 2D-3D
+// problems, scored with PICP's own gate (classify_item) and meant to be polished by PICP itself
+// (DESIGN.md §4.12).  Four launches:
+//   1. picp_pnp_samples_kernel  one lane per (problem, hypothesis): three distinct indices, a pure
+//                               counter-based function of (seed, problem, hypothesis) (picp_c.h);
+//   2. picp_pnp_solve_kernel    one lane per (problem, hypothesis), in double with contraction off:
+//                               Grunert's quartic, up to four float32 world-in-camera poses;
+//   3. picp_pnp_score_kernel    the hot path: a block keeps up to PNP_TILE correspondences of one
+//                               problem in registers and loops over the problem's poses (each one
+//                               wave-uniform: scalar loads); counts are ballots and scalar popcounts,
+//                               gathered per 64 hypotheses in LDS and added to the [hyp x root]
+//                               table with integer atomics (order-free);
+//   4. picp_pnp_select_kernel   one block per problem: the largest count, then the lowest
+//                               hypothesis, then the lowest root; the mask at the winner.
+// No block waits for another.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "picp_internal.h"
+#include "picp_item.h"
+#include "picp_launch.h"
+#include "picp_poly.h"
+#include "picp_pose.h"
+#include "picp_variant.h"
+
+#pragma clang fp contract(off)
+
+#define PNP_BS 256
+#define PNP_NPT 4
+#define PNP_TILE (PNP_BS * PNP_NPT)  // correspondences a score block keeps in registers
+#define PNP_HT 64                    // hypotheses per LDS count tile: PNP_HT * 4 roots == PNP_BS
+#define PNP_POSE 12                  // floats of a stored pose: R column-major, then t
+
+namespace {
+
+using picp::Cam;
+using picp::Pose;
+
+// splitmix64's output function of the state x + golden gamma
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// the sampling function of include/picp_c.h (n >= 3)
+__device__ __forceinline__ void sample_triple(uint64_t seed, uint32_t i, uint32_t h, uint32_t n, int32_t id[3]) {
+  const uint64_t key = mix64(seed ^ mix64(((uint64_t)i << 32) | h));
+  const uint64_t r0 = mix64(key) >> 32, r1 = mix64(key + 1) >> 32, r2 = mix64(key + 2) >> 32;
+  const uint32_t a = (uint32_t)((r0 * n) >> 32);
+  uint32_t b = (uint32_t)((r1 * (n - 1)) >> 32);
+  b += (b >= a) ? 1u : 0u;
+  uint32_t c = (uint32_t)((r2 * (n - 2)) >> 32);
+  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+  c += (c >= lo) ? 1u : 0u;
+  c += (c >= hi) ? 1u : 0u;
+  id[0] = (int32_t)a;
+  id[1] = (int32_t)b;
+  id[2] = (int32_t)c;
+}
+
+__device__ __forceinline__ double dot3(const double* a, const double* b) {
+  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+}
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// the orthonormal triad of a triangle as the columns e1 | e2 | e3 of M (row-major 3x3):
+// e1 along AB, e3 the normal, e2 = e3 x e1.  false when the triangle has no area.
+__device__ bool triad(const double* A, const double* B, const double* C, double M[9]) {
+  double e1[3], ac[3], e2[3], e3[3];
+  for (int k = 0; k < 3; ++k) {
+    e1[k] = B[k] - A[k];
+    ac[k] = C[k] - A[k];
+  }
+  const double n1 = sqrt(dot3(e1, e1));
+  if (!(n1 > 0.0)) return false;
+  for (int k = 0; k < 3; ++k) e1[k] /= n1;
+  cross3(e1, ac, e3);
+  const double n3 = sqrt(dot3(e3, e3));
+  if (!(n3 > 0.0)) return false;
+  for (int k = 0; k < 3; ++k) e3[k] /= n3;
+  cross3(e3, e1, e2);
+  for (int k = 0; k < 3; ++k) {
+    M[3 * k + 0] = e1[k];
+    M[3 * k + 1] = e2[k];
+    M[3 * k + 2] = e3[k];
+  }
+  return true;
+}
+
+// Grunert's P3P.  P: the three world points, px: their pixels, Kinv / K: the camera (K
+// column-major float).  Writes up to four poses (PNP_POSE floats each) and returns their number.
+// A root is kept when its three depths are positive, its pose is finite in float32 and, in
+// double, it reprojects its own three points within 1e-3 px: a root of the quartic that does
+// not solve the triangle (|cos(gamma) - v cos(alpha)| tiny, a repeated root the bisection only
+// brackets) is dropped there, so degenerate samples give no pose rather than a wrong one.
+__device__ int p3p_grunert(const double P[3][3], const double px[3][2], const double* Kinv, const float* K,
+                           float* out) {
+  double f[3][3];
+  for (int i = 0; i < 3; ++i) {
+    double nn = 0.0;
+    for (int r = 0; r < 3; ++r) {
+      f[i][r] = (Kinv[3 * r + 0] * px[i][0] + Kinv[3 * r + 1] * px[i][1]) + Kinv[3 * r + 2];
+      nn += f[i][r] * f[i][r];
+    }
+    nn = sqrt(nn);
+    if (!(nn > 0.0) || !(nn < INFINITY)) return 0;  // NaN or infinite pixel
+    for (int r = 0; r < 3; ++r) f[i][r] /= nn;
+  }
+  double d12[3], d13[3], d23[3], nrm[3];
+  for (int k = 0; k < 3; ++k) {
+    d12[k] = P[1][k] - P[0][k];
+    d13[k] = P[2][k] - P[0][k];
+    d23[k] = P[2][k] - P[1][k];
+  }
+  const double a2 = dot3(d23, d23), b2 = dot3(d13, d13), c2 = dot3(d12, d12);
+  cross3(d12, d13, nrm);
+  // coincident, collinear (sin^2 of the angle at P1 under 1e-10: float32 points on a line) or non-finite points
+  if (!(a2 > 0.0 && b2 > 0.0 && c2 > 0.0 && a2 < INFINITY && b2 < INFINITY && c2 < INFINITY &&
+        dot3(nrm, nrm) > 1e-10 * b2 * c2))
+    return 0;
+  const double ca = dot3(f[1], f[2]), cb = dot3(f[0], f[2]), cg = dot3(f[0], f[1]);
+  const double q = (a2 - c2) / b2, r = (a2 + c2) / b2, cb2 = c2 / b2, ab2 = a2 / b2;
+  double poly[5];
+  poly[4] = (q - 1.0) * (q - 1.0) - 4.0 * cb2 * ca * ca;
+  poly[3] = 4.0 * (q * (1.0 - q) * cb - (1.0 - r) * ca * cg + 2.0 * cb2 * ca * ca * cb);
+  poly[2] = 2.0 * (q * q - 1.0 + 2.0 * q * q * cb * cb + 2.0 * ((b2 - c2) / b2) * ca * ca - 4.0 * r * ca * cb * cg +
+                   2.0 * ((b2 - a2) / b2) * cg * cg);
+  poly[1] = 4.0 * (-q * (1.0 + q) * cb + 2.0 * ab2 * cg * cg * cb - (1.0 - r) * ca * cg);
+  poly[0] = (1.0 + q) * (1.0 + q) - 4.0 * ab2 * cg * cg;
+  for (int k = 0; k < 5; ++k)
+    if (!(fabs(poly[k]) < INFINITY)) return 0;
+  double vs[4];
+  const int nv = real_roots_t<4>(poly, 4, vs);
+  double W[9], pc[3] = {0.0, 0.0, 0.0};
+  if (!triad(P[0], P[1], P[2], W)) return 0;
+  for (int k = 0; k < 3; ++k) pc[k] = ((P[0][k] + P[1][k]) + P[2][k]) / 3.0;
+  int ns = 0;
+  for (int s = 0; s < nv; ++s) {
+    const double v = vs[s];
+    if (!(v > 0.0)) continue;
+    const double den = cg - v * ca;
+    if (!(fabs(den) >= 1e-9)) continue;
+    const double u = ((q - 1.0) * v * v - 2.0 * q * cb * v + 1.0 + q) / (2.0 * den);
+    const double d1 = 1.0 + v * v - 2.0 * v * cb;
+    if (!(u > 0.0 && d1 > 0.0)) continue;
+    const double s1 = sqrt(b2 / d1);
+    const double sc[3] = {s1, u * s1, v * s1};
+    double Q[3][3], qc[3];
+    for (int i = 0; i < 3; ++i)
+      for (int k = 0; k < 3; ++k) Q[i][k] = sc[i] * f[i][k];
+    double C[9], R[9], t[3];
+    if (!triad(Q[0], Q[1], Q[2], C)) continue;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) R[3 * i + j] = (C[3 * i] * W[3 * j] + C[3 * i + 1] * W[3 * j + 1]) + C[3 * i + 2] * W[3 * j + 2];
+    for (int k = 0; k < 3; ++k) qc[k] = ((Q[0][k] + Q[1][k]) + Q[2][k]) / 3.0;
+    for (int i = 0; i < 3; ++i) t[i] = qc[i] - dot3(R + 3 * i, pc);
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) {
+      double c[3], ph[3];
+      for (int k = 0; k < 3; ++k) c[k] = dot3(R + 3 * k, P[i]) + t[k];
+      for (int k = 0; k < 3; ++k) ph[k] = ((double)K[k] * c[0] + (double)K[3 + k] * c[1]) + (double)K[6 + k] * c[2];
+      const double eu = ph[0] / ph[2] - px[i][0], ev = ph[1] / ph[2] - px[i][1];
+      ok = ok && (eu * eu + ev * ev <= 1e-6);  // false for NaN
+    }
+    float* o = out + PNP_POSE * ns;
+    for (int j = 0; j < 3; ++j)
+      for (int i = 0; i < 3; ++i) o[3 * j + i] = (float)R[3 * i + j];
+    for (int i = 0; i < 3; ++i) o[9 + i] = (float)t[i];
+    for (int k = 0; k < PNP_POSE; ++k) ok = ok && (fabsf(o[k]) < INFINITY);
+    if (ok) ++ns;
+  }
+  return ns;
+}
+
+// whether correspondence j (< n) of the problem at element b is an inlier of pose T
+template <bool PIN>
+__device__ __forceinline__ bool pnp_inlier(const Pose& T, const Cam& C, float thr, float x, float y, float z, float u,
+                                           float v) {
+  float chi, iu, iv;
+  return picp::classify_item(T, C, thr, PIN, x, y, z, u, v, &chi, &iu, &iv) == PICP_CORR_INLIER;
+}
+
+}  // namespace
+
+// 1. the samples of (problem, hypothesis) g = p * hyp + h
+extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_samples_kernel(PnpArgs A, PnpItems I,
+                                                                             int32_t* __restrict__ samples) {
+  const int64_t g = (int64_t)blockIdx.x * PNP_BS + threadIdx.x;
+  if (g >= (int64_t)A.n_problems * A.hyp) return;
+  const int p = (int)(g / A.hyp), h = (int)(g % A.hyp);
+  const int64_t n = I.offs[p + 1] - I.offs[p];
+  int32_t id[3] = {0, 0, 0};
+  if (n >= 4) sample_triple(A.seed, (uint32_t)(A.prob0 + p), (uint32_t)h, (uint32_t)n, id);
+  for (int k = 0; k < 3; ++k) samples[3 * g + k] = id[k];
+}
+
+// 2. the poses of (problem, hypothesis) g
+extern "C" __global__ __launch_bounds__(64) void picp_pnp_solve_kernel(PnpArgs A, PnpItems I,
+                                                                       const int32_t* __restrict__ samples,
+                                                                       int32_t* __restrict__ n_roots,
+                                                                       float* __restrict__ hyp_T) {
+  const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (g >= (int64_t)A.n_problems * A.hyp) return;
+  const int p = (int)(g / A.hyp);
+  const int64_t n = I.offs[p + 1] - I.offs[p], b = I.base[p];
+  float* out = hyp_T + (size_t)g * 4 * PNP_POSE;
+  for (int k = 0; k < 4 * PNP_POSE; ++k) out[k] = 0.0f;
+  if (n < 4) {
+    n_roots[g] = 0;
+    return;
+  }
+  double P[3][3], px[3][2];
+  for (int k = 0; k < 3; ++k) {
+    const int64_t j = b + samples[3 * g + k];
+    P[k][0] = (double)I.x[j * I.sx];
+    P[k][1] = (double)I.y[j * I.sx];
+    P[k][2] = (double)I.z[j * I.sx];
+    px[k][0] = (double)I.u[j * I.su];
+    px[k][1] = (double)I.v[j * I.su];
+  }
+  n_roots[g] = p3p_grunert(P, px, A.Kinv, A.K, out);
+}
+
+// 3. the inlier counts.  Block blockIdx.x holds correspondences [first, first + PNP_TILE) of
+// problem blk[blockIdx.x].x; slice blockIdx.y of gridDim.y takes every gridDim.y-th tile of
+// PNP_HT hypotheses.  cnt ([hyp x 4] per problem) is zeroed by the caller.
+template <bool PIN>
+__device__ __forceinline__ void pnp_score(const PnpArgs& A, const PnpItems& I, const int2* __restrict__ blk,
+                                          const int32_t* __restrict__ n_roots, const float* __restrict__ hyp_T,
+                                          int32_t* __restrict__ cnt, int* s_cnt) {
+  const int tid = threadIdx.x;
+  const int2 bi = blk[blockIdx.x];
+  const int p = bi.x, first = bi.y;
+  const int n = (int)(I.offs[p + 1] - I.offs[p]);
+  const int64_t b = I.base[p];
+  Cam C;
+  picp::cam_load(A.K, A.maxx, A.maxy, C);
+  float x[PNP_NPT], y[PNP_NPT], z[PNP_NPT], u[PNP_NPT], v[PNP_NPT];
+  bool in[PNP_NPT];
+#pragma unroll
+  for (int k = 0; k < PNP_NPT; ++k) {
+    const int64_t j = (int64_t)first + k * PNP_BS + tid;  // n may be INT32_MAX
+    in[k] = j < n;
+    const int64_t e = b + (in[k] ? j : first);  // a lane past the end re-reads a valid item, masked below
+    x[k] = I.x[e * I.sx];
+    y[k] = I.y[e * I.sx];
+    z[k] = I.z[e * I.sx];
+    u[k] = I.u[e * I.su];
+    v[k] = I.v[e * I.su];
+  }
+  const size_t ph0 = (size_t)p * A.hyp;
+  for (int h0 = blockIdx.y * PNP_HT; h0 < A.hyp; h0 += gridDim.y * PNP_HT) {
+    s_cnt[tid] = 0;
+    __syncthreads();
+    const int h1 = (h0 + PNP_HT < A.hyp) ? h0 + PNP_HT : A.hyp;
+    for (int h = h0; h < h1; ++h) {
+      const int nr = n_roots[ph0 + h];  // wave-uniform: scalar loads, as the pose below
+      for (int r = 0; r < nr; ++r) {
+        const float* Tp = hyp_T + ((ph0 + h) * 4 + r) * PNP_POSE;
+        Pose T;
+        picp::pose_load(Tp, Tp + 9, T);
+        unsigned c = 0;
+#pragma unroll
+        for (int k = 0; k < PNP_NPT; ++k) {
+          const bool inl = in[k] & pnp_inlier<PIN>(T, C, A.threshold, x[k], y[k], z[k], u[k], v[k]);
+          c += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(inl));
+        }
+        if ((tid & 63) == 0 && c) atomicAdd(&s_cnt[(h - h0) * 4 + r], (int)c);
+      }
+    }
+    __syncthreads();
+    const int mine = s_cnt[tid];  // entry (h0 + tid / 4, root tid % 4)
+    if (mine) atomicAdd(&cnt[(ph0 + h0) * 4 + tid], mine);
+    __syncthreads();
+  }
+}
+
+extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_score_kernel(PnpArgs A, PnpItems I,
+                                                                           const int2* __restrict__ blk,
+                                                                           const int32_t* __restrict__ n_roots,
+                                                                           const float* __restrict__ hyp_T,
+                                                                           int32_t* __restrict__ cnt) {
+  __shared__ int s_cnt[PNP_HT * 4];  // counts of one tile of hypotheses, entry 4 (h - h0) + root
+  if (A.pinhole)
+    pnp_score<true>(A, I, blk, n_roots, hyp_T, cnt, s_cnt);
+  else
+    pnp_score<false>(A, I, blk, n_roots, hyp_T, cnt, s_cnt);
+}
+
+// 4. the winner of problem blockIdx.x and the mask at it
+extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_select_kernel(
+    PnpArgs A, PnpItems I, const int32_t* __restrict__ n_roots, const float* __restrict__ hyp_T,
+    const int32_t* __restrict__ cnt, float* __restrict__ T_out, int32_t* __restrict__ inliers,
+    int32_t* __restrict__ found, uint8_t* __restrict__ mask) {
+  __shared__ unsigned long long s_key[PNP_BS / 64];
+  __shared__ unsigned long long s_win;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int n = (int)(I.offs[p + 1] - I.offs[p]);
+  const size_t ph0 = (size_t)p * A.hyp;
+  // key of entry e = 4 h + r (r < n_roots[h]): (count + 1) above ~e, so the maximum is the
+  // largest count at the lowest entry and 0 means no entry; it does not depend on who finds it
+  unsigned long long key = 0;
+  for (int64_t e = tid; e < (int64_t)A.hyp * 4; e += PNP_BS) {
+    if ((int)(e & 3) >= n_roots[ph0 + (e >> 2)]) continue;
+    const unsigned long long k = ((unsigned long long)((unsigned)cnt[ph0 * 4 + e] + 1u) << 32) | (unsigned)~(unsigned)e;
+    key = k > key ? k : key;
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = __shfl_xor(key, m);
+    key = o > key ? o : key;
+  }
+  if ((tid & 63) == 0) s_key[tid >> 6] = key;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < PNP_BS / 64; ++w) key = s_key[w] > key ? s_key[w] : key;
+    s_win = key;
+  }
+  __syncthreads();
+  key = s_win;
+  const int best = key ? (int)(key >> 32) - 1 : 0;
+  const bool ok = key != 0 && n >= 4 && best >= A.min_inliers;
+  const float* Tp = hyp_T + (ph0 * 4 + (unsigned)~(unsigned)key) * PNP_POSE;  // read only when ok
+  if (tid < 16) {
+    float val = (tid % 5 == 0) ? 1.0f : 0.0f;  // the identity, and the bottom row of a pose
+    const int r = tid & 3, c = tid >> 2;
+    if (ok && r < 3) val = (c < 3) ? Tp[3 * c + r] : Tp[9 + r];
+    T_out[16 * (size_t)p + tid] = val;
+  }
+  if (tid == 0) {
+    inliers[p] = best;
+    found[p] = ok ? 1 : 0;
+  }
+  if (!mask) return;
+  const int64_t b = I.base[p], o = I.offs[p];
+  if (!ok) {
+    for (int j = tid; j < n; j += PNP_BS) mask[o + j] = 0;
+    return;
+  }
+  Pose T;
+  picp::pose_load(Tp, Tp + 9, T);
+  Cam C;
+  picp::cam_load(A.K, A.maxx, A.maxy, C);
+  for (int j = tid; j < n; j += PNP_BS) {
+    const int64_t e = b + j;
+    const float x = I.x[e * I.sx], y = I.y[e * I.sx], z = I.z[e * I.sx], u = I.u[e * I.su], v = I.v[e * I.su];
+    const bool inl = A.pinhole ? pnp_inlier<true>(T, C, A.threshold, x, y, z, u, v)
+                               : pnp_inlier<false>(T, C, A.threshold, x, y, z, u, v);
+    mask[o + j] = inl ? 1 : 0;
+  }
+}
+
+// ------------------------------- host launch wrappers -------------------------------
+// Every per-(problem, hypothesis) array is indexed p * hyp + h; problems sit on grid x.
+extern "C" int picp_pnp_score_tile(void) { return PNP_TILE; }
+extern "C" int picp_pnp_hyp_tile(void) { return PNP_HT; }
+
+extern "C" hipError_t picp_launch_pnp_samples(hipStream_t stream, const PnpArgs* A, const PnpItems* I,
+                                              int32_t* samples) {
+  const int64_t g = (int64_t)A->n_problems * A->hyp;
+  hipLaunchKernelGGL(picp_pnp_samples_kernel, dim3((unsigned)((g + PNP_BS - 1) / PNP_BS)), dim3(PNP_BS), 0, stream, *A,
+                     *I, samples);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t picp_launch_pnp_solve(hipStream_t stream, const PnpArgs* A, const PnpItems* I,
+                                            const int32_t* samples, int32_t* n_roots, float* hyp_T) {
+  const int64_t g = (int64_t)A->n_problems * A->hyp;
+  hipLaunchKernelGGL(picp_pnp_solve_kernel, dim3((unsigned)((g + 63) / 64)), dim3(64), 0, stream, *A, *I, samples,
+                     n_roots, hyp_T);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t picp_launch_pnp_score(hipStream_t stream, const PnpArgs* A, const PnpItems* I, int nb,
+                                            const int2* blk, int hsplit, const int32_t* n_roots, const float* hyp_T,
+                                            int32_t* cnt) {
+  if (nb <= 0) return hipSuccess;  // no problem has a correspondence
+  PnpArgs a = *A;
+  a.pinhole = picp_use_pinhole(a.K) ? 1 : 0;  // the camera path the classify pass takes
+  hipLaunchKernelGGL(picp_pnp_score_kernel, dim3((unsigned)nb, (unsigned)hsplit), dim3(PNP_BS), 0, stream, a, *I, blk,
+                     n_roots, hyp_T, cnt);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t picp_launch_pnp_select(hipStream_t stream, const PnpArgs* A, const PnpItems* I,
+                                             const int32_t* n_roots, const float* hyp_T, const int32_t* cnt,
+                                             float* T_out, int32_t* inliers, int32_t* found, uint8_t* mask) {
+  PnpArgs a = *A;
+  a.pinhole = picp_use_pinhole(a.K) ? 1 : 0;
+  hipLaunchKernelGGL(picp_pnp_select_kernel, dim3((unsigned)A->n_problems), dim3(PNP_BS), 0, stream, a, *I, n_roots,
+                     hyp_T, cnt, T_out, inliers, found, mask);
+  return hipGetLastError();
+}

@@ -57,6 +57,7 @@ EXPORTED = [
     "picp_adjust_params_default", "picp_refine_set_fixed_poses", "picp_refine_run_poses", "picp_refine_adjust",
     "picp_refine_get_poses", "picp_refine_get_pose_stats", "picp_refine_get_pose_view", "picp_refine_get_sweeps",
     "picp_refine_adjust_time", "picp_vo_adjust", "picp_vo_get_adjusted_poses_wc", "picp_vo_get_adjusted_map",
+    "picp_pnp_params_default", "picp_pnp_batch", "picp_pnp_batch_debug", "picp_pnp_batch_time", "picp_relocalize",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -106,6 +107,12 @@ class AdjustSweep(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PnpParams(ctypes.Structure):
+    """picp_pnp_params (include/picp_c.h): the P3P RANSAC's gate, hypothesis count and seed."""
+    _fields_ = [("threshold", ctypes.c_float), ("hypotheses", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
 _lib = None
 # picp_exchange_fn (include/picp_c.h): int (*)(void* user, const void* send, void* recv, size_t bytes)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -129,6 +136,7 @@ def lib():
     dp = ctypes.POINTER(ctypes.c_double)
     sp = ctypes.POINTER(Stats)
     pp = ctypes.POINTER(Params)
+    i32p, u8p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
     sig = {
         "picp_params_default": ([pp], None),
         "picp_abi_version": ([], i),
@@ -230,6 +238,12 @@ def lib():
         "picp_vo_adjust": ([vp, ctypes.POINTER(AdjustParams)], i),
         "picp_vo_get_adjusted_poses_wc": ([vp, fp], i),
         "picp_vo_get_adjusted_map": ([vp, i, i64, fp, sp, ctypes.POINTER(i64)], i),
+        "picp_pnp_params_default": ([ctypes.POINTER(PnpParams)], None),
+        "picp_pnp_batch": ([i, i, ctypes.POINTER(i64), fp, fp, fp, i, i, ctypes.POINTER(PnpParams), fp, i32p, i32p, u8p], i),
+        "picp_pnp_batch_debug": ([i, i, ctypes.POINTER(i64), fp, fp, fp, i, i, ctypes.POINTER(PnpParams), fp, i32p, i32p,
+                                  u8p, i32p, i32p, fp, i32p], i),
+        "picp_pnp_batch_time": ([i, i, ctypes.POINTER(i64), fp, fp, fp, i, i, ctypes.POINTER(PnpParams), i, fp], i),
+        "picp_relocalize": ([vp, ctypes.POINTER(PnpParams), i32p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -391,6 +405,16 @@ class PICPSolver:
                                    counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return {"state": state[:m], "chi2": chi2[:m], "uv": uv[:2 * m].reshape(-1, 2),
                 "inlier_idx": idx[:int(counts[1])], "counts": counts}
+
+    def relocalize(self, correspondences, threshold=9.0, hypotheses=256, min_inliers=4, seed=0):
+        """picp_relocalize: P3P RANSAC on the correspondences, no prior needed.  On success the pose
+        is the winner (polish it with solve()).  Returns (found, inliers); a failure leaves the pose
+        and the stats as they were."""
+        self.set_correspondences(correspondences)
+        prm = PnpParams(threshold, hypotheses, min_inliers, 0, seed)
+        n = ctypes.c_int32(0)
+        rc = _check(lib().picp_relocalize(self._h, ctypes.byref(prm), ctypes.byref(n)), allow=(TOO_FEW_INLIERS,))
+        return rc == OK, n.value
 
 
 class Batch:
@@ -706,6 +730,74 @@ def essential_recover_pose_batch(p1_list, p2_list, K=None, prob=0.999, threshold
             d["mask"] = mask[offs[i]:offs[i + 1]].astype(bool)
         out.append(d)
     return out
+
+
+def _pnp_pack(xyz_list, uv_list):
+    offs = np.zeros(len(xyz_list) + 1, np.int64)
+    offs[1:] = np.cumsum([len(x) for x in xyz_list])
+    n = int(offs[-1])
+    xyz = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in xyz_list])
+                               if n else np.zeros((0, 3), np.float32))
+    uv = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 2) for x in uv_list])
+                              if n else np.zeros((0, 2), np.float32))
+    assert len(xyz) == len(uv) == n
+    return offs, xyz, uv
+
+
+def pnp_ransac_batch(xyz_list, uv_list, K=None, rows=480, cols=640, threshold=9.0, hypotheses=256, min_inliers=4,
+                     seed=0, want_mask=False, debug=False, device=0):
+    """picp_pnp_batch: absolute pose without a prior for many 2D-3D problems (P3P inside RANSAC,
+    scored with the solver's gate at `threshold`).  Returns per problem a dict with T (4x4
+    world-in-camera; the identity when found is False), inliers, found (and mask); with debug also
+    samples (H, 3), n_roots (H,), hyp_T (H, 4, 4, 4) and hyp_count (H, 4)."""
+    K = K_REF if K is None else K
+    P = len(xyz_list)
+    offs, xyz, uv = _pnp_pack(xyz_list, uv_list)
+    n, H = int(offs[-1]), hypotheses
+    prm = PnpParams(threshold, hypotheses, min_inliers, 0, seed)
+    T = np.zeros(16 * max(P, 1), np.float32)
+    inl = np.zeros(max(P, 1), np.int32)
+    found = np.zeros(max(P, 1), np.int32)
+    mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+    u8 = ctypes.POINTER(ctypes.c_uint8)
+    args = [device, P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _fptr(xyz) if n else None,
+            _fptr(uv) if n else None, _fptr(k_to_c(K)), rows, cols, ctypes.byref(prm), _fptr(T), _i32ptr(inl),
+            _i32ptr(found), mask.ctypes.data_as(u8) if want_mask else None]
+    if debug:
+        G = max(P * max(H, 0), 1)
+        smp = np.zeros(3 * G, np.int32)
+        nr = np.zeros(G, np.int32)
+        hT = np.zeros(64 * G, np.float32)
+        hc = np.zeros(4 * G, np.int32)
+        _check(lib().picp_pnp_batch_debug(*args, _i32ptr(smp), _i32ptr(nr), _fptr(hT), _i32ptr(hc)))
+    else:
+        _check(lib().picp_pnp_batch(*args))
+    out = []
+    for i in range(P):
+        d = {"T": pose_from_c(T[16 * i:16 * i + 16]), "inliers": int(inl[i]), "found": bool(found[i])}
+        if want_mask:
+            d["mask"] = mask[offs[i]:offs[i + 1]].astype(bool)
+        if debug:
+            g = slice(i * H, (i + 1) * H)
+            d["samples"] = smp.reshape(-1, 3)[g]
+            d["n_roots"] = nr[g]
+            d["hyp_T"] = np.transpose(hT.reshape(-1, 4, 4, 4)[g], (0, 1, 3, 2)).copy()
+            d["hyp_count"] = hc.reshape(-1, 4)[g]
+        out.append(d)
+    return out
+
+
+def pnp_ransac_time(xyz_list, uv_list, reps, K=None, rows=480, cols=640, threshold=9.0, hypotheses=256, seed=0,
+                    device=0):
+    """picp_pnp_batch_time: mean device time in us of the (samples, solve, score, select) stages."""
+    K = K_REF if K is None else K
+    offs, xyz, uv = _pnp_pack(xyz_list, uv_list)
+    prm = PnpParams(threshold, hypotheses, 4, 0, seed)
+    us = np.zeros(4, np.float32)
+    _check(lib().picp_pnp_batch_time(device, len(xyz_list), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                     _fptr(xyz), _fptr(uv), _fptr(k_to_c(K)), rows, cols, ctypes.byref(prm), reps,
+                                     _fptr(us)))
+    return tuple(float(x) for x in us)
 
 
 class VOSequence:

@@ -559,6 +559,68 @@ int picp_vo_debug_matches(picp_vo_t* h, int which, int32_t* dst);
  * index in allocation order) + (0 before / 1 after) of the first changed pad, or -1. */
 int picp_vo_debug_guard(picp_vo_t* h, int64_t* bad_bytes, int* bad_buffer);
 
+/* ---------------- absolute pose without a prior: P3P RANSAC ---------------- */
+/* "Here are 2D-3D matches against a map, where is the camera?" when no nearby pose is known (lost
+ * tracking, a new frame against an existing map): a minimal absolute-pose solver (Grunert's P3P,
+ * in double) inside RANSAC, scored with the solver's own gate (a correspondence counts when it is
+ * PICP_CORR_INLIER at the hypothesis with `threshold`), to be polished by picp_solve /
+ * picp_batch_solve from the returned pose.  All hypotheses are scored (no adaptive stop, no local
+ * optimisation).  Problems are ragged: problem i owns correspondences [offs[i], offs[i+1]) of xyz
+ * (3 floats each) and uv (2 floats each); offs[0] = 0.
+ *
+ * The samples.  Hypothesis h of problem i (its position in the batch) with n >= 4 correspondences
+ * draws three distinct indices in [0, n) as a pure function of (seed, i, h).  With 64-bit wrapping
+ * arithmetic and
+ *   mix(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)      (splitmix64)
+ *   key = mix(seed ^ mix((i << 32) | h)),  r_j = mix(key + j) >> 32  for j = 0, 1, 2:
+ *   a = (r_0 * n) >> 32
+ *   b = (r_1 * (n - 1)) >> 32,  then b += 1 if b >= a
+ *   c = (r_2 * (n - 2)) >> 32,  then c += 1 if c >= min(a, b),  then c += 1 if c >= max(a, b)
+ * (skipping past the indices already chosen: no rejection loop).  The triple is (a, b, c).
+ *
+ * The result of problem i: the (hypothesis, root) with the largest count, then the lowest
+ * hypothesis, then the lowest root.  found[i] = 1 and T_out its float32 world-in-camera pose -- the
+ * pose that was scored -- when n >= 4, some hypothesis has a root and the count >= min_inliers;
+ * otherwise found[i] = 0, T_out the identity, mask all 0, and inliers[i] the best count seen (0
+ * when no hypothesis has a root).  mask (nullable, one byte per correspondence): 1 where the
+ * correspondence is an inlier at T_out.  The same inputs give the same bits on every call.
+ * n_problems * hypotheses is limited to 2^24 per call. */
+typedef struct picp_pnp_params {
+  float threshold;      /* squared pixels, the solver's strict gate; default 9 */
+  int32_t hypotheses;   /* per problem, default 256, 1..65536 */
+  int32_t min_inliers;  /* default 4 */
+  int32_t reserved;
+  uint64_t seed;        /* default 0 */
+} picp_pnp_params;
+
+void picp_pnp_params_default(picp_pnp_params* p);
+
+/* prm NULL = picp_pnp_params_default.  n_problems == 0 returns PICP_OK. */
+int picp_pnp_batch(int device, int n_problems, const int64_t* offs, const float* xyz, const float* uv,
+                   const float K[9], int rows, int cols, const picp_pnp_params* prm, float* T_out,
+                   int32_t* inliers, int32_t* found, uint8_t* mask);
+
+/* picp_pnp_batch with the intermediate arrays, for tests; every output pointer may be NULL.  With
+ * H = hypotheses, per problem: samples 3 H indices, n_roots H, hyp_T H x 4 poses of 16 floats
+ * (column-major 4x4; zero beyond a hypothesis' n_roots), hyp_count H x 4 (0 beyond n_roots). */
+int picp_pnp_batch_debug(int device, int n_problems, const int64_t* offs, const float* xyz, const float* uv,
+                         const float K[9], int rows, int cols, const picp_pnp_params* prm, float* T_out,
+                         int32_t* inliers, int32_t* found, uint8_t* mask, int32_t* samples, int32_t* n_roots,
+                         float* hyp_T, int32_t* hyp_count);
+
+/* mean device time in us of the four stages (samples, solve, score, select) over `reps`
+ * repetitions after one untimed pass; us[4] */
+int picp_pnp_batch_time(int device, int n_problems, const int64_t* offs, const float* xyz, const float* uv,
+                        const float K[9], int rows, int cols, const picp_pnp_params* prm, int reps, float* us);
+
+/* Single frame: the RANSAC above on the handle's points and current correspondences (problem
+ * index 0).  On success the handle's pose is set to the winner, *inliers (nullable) to its count
+ * and PICP_OK returned; when nothing is found PICP_TOO_FEW_INLIERS is returned, *inliers is the
+ * best count seen and the handle's pose keeps its bits.  The caller's picp_stats are not touched
+ * either way.  Follow with picp_solve. */
+int picp_relocalize(picp_t* h, const picp_pnp_params* prm, int32_t* inliers);
+
 /* ---------------- self-test ---------------- */
 /* The projection's reciprocal 1/z must be the correctly rounded one (src/camera.h:30; the
  * chi2 gate is bit-exact): the kernels use a 3-instruction form, valid for every float in

@@ -26,6 +26,11 @@
 
 namespace pr {
 
+//! picp_pnp_params with the defaults filled in (threshold 9, 256 hypotheses, min_inliers 4, seed 0)
+struct PnpParams : picp_pnp_params {
+  PnpParams() { picp_pnp_params_default(this); }
+};
+
 class PICPSolver {
  public:
   EIGEN_MAKE_ALIGNED_OPERATOR_NEW
@@ -148,6 +153,30 @@ class PICPSolver {
     for (int64_t k = 0; k < counts[1]; ++k) out.push_back(correspondences[(size_t)idx[(size_t)k]]);
     return (int)counts[1];
   }
+  //! absolute pose without a prior (picp_relocalize: P3P RANSAC on the current correspondences,
+  //! scored with the solver's gate at prm.threshold).  true: the camera holds the winner, to be
+  //! polished by oneRound / solve; false: nothing found (or an error, lastStatus()), the pose and
+  //! the stats are untouched.  lastRelocalizeInliers() is the best count either way.
+  bool relocalize(const PnpParams& prm = PnpParams()) {
+    if (!_h) return false;
+    _status = picp_relocalize(_h, &prm, &_reloc_inliers);
+    if (_status == PICP_TOO_FEW_INLIERS) return false;
+    if (_status != PICP_OK) {
+      std::cerr << "picp_relocalize: " << picp_last_error() << std::endl;
+      return false;
+    }
+    pull_pose();
+    return true;
+  }
+  bool relocalize(const IntPairVector& correspondences, const PnpParams& prm = PnpParams()) {
+    if (!_h) return false;
+    if (!check(picp_set_correspondences(_h, reinterpret_cast<const int32_t*>(correspondences.data()),
+                                        (int64_t)correspondences.size()),
+               "picp_set_correspondences"))
+      return false;
+    return relocalize(prm);
+  }
+  int lastRelocalizeInliers() const { return _reloc_inliers; }
   void setDamping(float d) { _damping = d; }
   void setMinNumInliers(int n) { _min_num_inliers = n; }
   int lastStatus() const { return _status; }
@@ -184,6 +213,7 @@ class PICPSolver {
     _min_num_inliers = o._min_num_inliers;
     _stats = o._stats;
     _status = o._status;
+    _reloc_inliers = o._reloc_inliers;
   }
   void take(PICPSolver& o) {
     copy_state(o);
@@ -203,6 +233,7 @@ class PICPSolver {
   int _min_num_inliers;          //< if less inliers than this value, the solver stops
   picp_stats _stats = {0.f, 0.f, 0, 1, 0, 0, 0, 0};
   int _status = PICP_OK;
+  int32_t _reloc_inliers = 0;
 };
 
 }  // namespace pr
