@@ -4,7 +4,7 @@
 //   1. picp_pnp_samples_kernel  one lane per (problem, hypothesis): three distinct indices, a pure
 //                               counter-based function of (seed, problem, hypothesis) (picp_c.h);
 //   2. picp_pnp_solve_kernel    one lane per (problem, hypothesis), in double with contraction off:
-//                               Grunert's quartic, up to four float32 world-in-camera poses;
+//                               Grunert's quartic (picp_p3p.h), up to four float32 world-in-camera poses;
 //   3. picp_pnp_score_kernel    the hot path: a block keeps up to PNP_TILE correspondences of one
 //                               problem in registers and loops over the problem's poses (each one
 //                               wave-uniform: scalar loads); counts are ballots and scalar popcounts,
@@ -21,7 +21,7 @@
 #include "picp_internal.h"
 #include "picp_item.h"
 #include "picp_launch.h"
-#include "picp_poly.h"
+#include "picp_p3p.h"
 #include "picp_pose.h"
 #include "picp_variant.h"
 
@@ -31,7 +31,6 @@
 #define PNP_NPT 4
 #define PNP_TILE (PNP_BS * PNP_NPT)  // correspondences a score block keeps in registers
 #define PNP_HT 64                    // hypotheses per LDS count tile: PNP_HT * 4 roots == PNP_BS
-#define PNP_POSE 12                  // floats of a stored pose: R column-major, then t
 
 namespace {
 
@@ -60,125 +59,6 @@ __device__ __forceinline__ void sample_triple(uint64_t seed, uint32_t i, uint32_
   id[0] = (int32_t)a;
   id[1] = (int32_t)b;
   id[2] = (int32_t)c;
-}
-
-__device__ __forceinline__ double dot3(const double* a, const double* b) {
-  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// the orthonormal triad of a triangle as the columns e1 | e2 | e3 of M (row-major 3x3):
-// e1 along AB, e3 the normal, e2 = e3 x e1.  false when the triangle has no area.
-__device__ bool triad(const double* A, const double* B, const double* C, double M[9]) {
-  double e1[3], ac[3], e2[3], e3[3];
-  for (int k = 0; k < 3; ++k) {
-    e1[k] = B[k] - A[k];
-    ac[k] = C[k] - A[k];
-  }
-  const double n1 = sqrt(dot3(e1, e1));
-  if (!(n1 > 0.0)) return false;
-  for (int k = 0; k < 3; ++k) e1[k] /= n1;
-  cross3(e1, ac, e3);
-  const double n3 = sqrt(dot3(e3, e3));
-  if (!(n3 > 0.0)) return false;
-  for (int k = 0; k < 3; ++k) e3[k] /= n3;
-  cross3(e3, e1, e2);
-  for (int k = 0; k < 3; ++k) {
-    M[3 * k + 0] = e1[k];
-    M[3 * k + 1] = e2[k];
-    M[3 * k + 2] = e3[k];
-  }
-  return true;
-}
-
-// Grunert's P3P.  P: the three world points, px: their pixels, Kinv / K: the camera (K
-// column-major float).  Writes up to four poses (PNP_POSE floats each) and returns their number.
-// A root is kept when its three depths are positive, its pose is finite in float32 and, in
-// double, it reprojects its own three points within 1e-3 px: a root of the quartic that does
-// not solve the triangle (|cos(gamma) - v cos(alpha)| tiny, a repeated root the bisection only
-// brackets) is dropped there, so degenerate samples give no pose rather than a wrong one.
-__device__ int p3p_grunert(const double P[3][3], const double px[3][2], const double* Kinv, const float* K,
-                           float* out) {
-  double f[3][3];
-  for (int i = 0; i < 3; ++i) {
-    double nn = 0.0;
-    for (int r = 0; r < 3; ++r) {
-      f[i][r] = (Kinv[3 * r + 0] * px[i][0] + Kinv[3 * r + 1] * px[i][1]) + Kinv[3 * r + 2];
-      nn += f[i][r] * f[i][r];
-    }
-    nn = sqrt(nn);
-    if (!(nn > 0.0) || !(nn < INFINITY)) return 0;  // NaN or infinite pixel
-    for (int r = 0; r < 3; ++r) f[i][r] /= nn;
-  }
-  double d12[3], d13[3], d23[3], nrm[3];
-  for (int k = 0; k < 3; ++k) {
-    d12[k] = P[1][k] - P[0][k];
-    d13[k] = P[2][k] - P[0][k];
-    d23[k] = P[2][k] - P[1][k];
-  }
-  const double a2 = dot3(d23, d23), b2 = dot3(d13, d13), c2 = dot3(d12, d12);
-  cross3(d12, d13, nrm);
-  // coincident, collinear (sin^2 of the angle at P1 under 1e-10: float32 points on a line) or non-finite points
-  if (!(a2 > 0.0 && b2 > 0.0 && c2 > 0.0 && a2 < INFINITY && b2 < INFINITY && c2 < INFINITY &&
-        dot3(nrm, nrm) > 1e-10 * b2 * c2))
-    return 0;
-  const double ca = dot3(f[1], f[2]), cb = dot3(f[0], f[2]), cg = dot3(f[0], f[1]);
-  const double q = (a2 - c2) / b2, r = (a2 + c2) / b2, cb2 = c2 / b2, ab2 = a2 / b2;
-  double poly[5];
-  poly[4] = (q - 1.0) * (q - 1.0) - 4.0 * cb2 * ca * ca;
-  poly[3] = 4.0 * (q * (1.0 - q) * cb - (1.0 - r) * ca * cg + 2.0 * cb2 * ca * ca * cb);
-  poly[2] = 2.0 * (q * q - 1.0 + 2.0 * q * q * cb * cb + 2.0 * ((b2 - c2) / b2) * ca * ca - 4.0 * r * ca * cb * cg +
-                   2.0 * ((b2 - a2) / b2) * cg * cg);
-  poly[1] = 4.0 * (-q * (1.0 + q) * cb + 2.0 * ab2 * cg * cg * cb - (1.0 - r) * ca * cg);
-  poly[0] = (1.0 + q) * (1.0 + q) - 4.0 * ab2 * cg * cg;
-  for (int k = 0; k < 5; ++k)
-    if (!(fabs(poly[k]) < INFINITY)) return 0;
-  double vs[4];
-  const int nv = real_roots_t<4>(poly, 4, vs);
-  double W[9], pc[3] = {0.0, 0.0, 0.0};
-  if (!triad(P[0], P[1], P[2], W)) return 0;
-  for (int k = 0; k < 3; ++k) pc[k] = ((P[0][k] + P[1][k]) + P[2][k]) / 3.0;
-  int ns = 0;
-  for (int s = 0; s < nv; ++s) {
-    const double v = vs[s];
-    if (!(v > 0.0)) continue;
-    const double den = cg - v * ca;
-    if (!(fabs(den) >= 1e-9)) continue;
-    const double u = ((q - 1.0) * v * v - 2.0 * q * cb * v + 1.0 + q) / (2.0 * den);
-    const double d1 = 1.0 + v * v - 2.0 * v * cb;
-    if (!(u > 0.0 && d1 > 0.0)) continue;
-    const double s1 = sqrt(b2 / d1);
-    const double sc[3] = {s1, u * s1, v * s1};
-    double Q[3][3], qc[3];
-    for (int i = 0; i < 3; ++i)
-      for (int k = 0; k < 3; ++k) Q[i][k] = sc[i] * f[i][k];
-    double C[9], R[9], t[3];
-    if (!triad(Q[0], Q[1], Q[2], C)) continue;
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) R[3 * i + j] = (C[3 * i] * W[3 * j] + C[3 * i + 1] * W[3 * j + 1]) + C[3 * i + 2] * W[3 * j + 2];
-    for (int k = 0; k < 3; ++k) qc[k] = ((Q[0][k] + Q[1][k]) + Q[2][k]) / 3.0;
-    for (int i = 0; i < 3; ++i) t[i] = qc[i] - dot3(R + 3 * i, pc);
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) {
-      double c[3], ph[3];
-      for (int k = 0; k < 3; ++k) c[k] = dot3(R + 3 * k, P[i]) + t[k];
-      for (int k = 0; k < 3; ++k) ph[k] = ((double)K[k] * c[0] + (double)K[3 + k] * c[1]) + (double)K[6 + k] * c[2];
-      const double eu = ph[0] / ph[2] - px[i][0], ev = ph[1] / ph[2] - px[i][1];
-      ok = ok && (eu * eu + ev * ev <= 1e-6);  // false for NaN
-    }
-    float* o = out + PNP_POSE * ns;
-    for (int j = 0; j < 3; ++j)
-      for (int i = 0; i < 3; ++i) o[3 * j + i] = (float)R[3 * i + j];
-    for (int i = 0; i < 3; ++i) o[9 + i] = (float)t[i];
-    for (int k = 0; k < PNP_POSE; ++k) ok = ok && (fabsf(o[k]) < INFINITY);
-    if (ok) ++ns;
-  }
-  return ns;
 }
 
 // whether correspondence j (< n) of the problem at element b is an inlier of pose T

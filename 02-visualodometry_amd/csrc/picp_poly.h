@@ -1,8 +1,8 @@
 // picp_poly.h -- real polynomials in double for the one-lane-per-hypothesis solvers
-// (picp_essential.hip: Nister's degree-10 polynomial; picp_pnp.hip: Grunert's quartic).
+// (picp_essential.hip: Nister's degree-10 polynomial; picp_p3p.h: Grunert's quartic).
 #pragma once
-// PICP_POLY_HOST: a plain host build (bin/poly_check compares the two root finders on the CPU;
-// compile it with -ffp-contract=off)
+// PICP_POLY_HOST: a plain host build (bin/poly_check compares the two root finders on the CPU,
+// bin/p3p_check runs the P3P; compile with -ffp-contract=off)
 #ifdef PICP_POLY_HOST
 #define PICP_POLY_FN
 #else
@@ -85,6 +85,10 @@ PICP_POLY_FN int real_roots(const double* p_in, int d, double* roots) {
 // instead of being read from the derivative table in every Horner step.  A copy of the loop above
 // rather than a parameter of it: as one template the essential unit's code object changed.
 // tests/poly_check/poly_main.cpp (bin/poly_check) holds the two to the same bits: change both.
+// A third copy of the loop's last level is p3p_quartic_roots (picp_p3p.h): it bisects the quartic
+// between critical points it keeps for its caller.  Not held to these bits (its critical points come
+// from a call of real_roots_t<4> on the derivative, with that polynomial's own root bound);
+// tests/test_pnp_cpu.py holds it to known roots through bin/poly_check --roots.  Change it too.
 template <int NR>
 PICP_POLY_FN int real_roots_t(const double* p_in, int d, double* roots) {
   double p[NR + 1];

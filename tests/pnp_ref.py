@@ -54,10 +54,47 @@ def _triad(A, B, C):
     return np.column_stack([e1, np.cross(e3, e1), e3])
 
 
+def _conic_residual(g, x, y):
+    """The two distance-ratio conics divided by b^2 at x = s2/s1 - 1, y = s3/s1 - 1, as sums of
+    small terms (csrc/picp_p3p.h p3p_residual) -> (F, the sum of the magnitudes of F's terms)."""
+    ma, mb, mg, cb2, ab2 = g
+    t0, t1 = x * x + 2 * (1 + x) * mg, y * y + 2 * (1 + y) * mb
+    t2 = (x - y) ** 2 + 2 * (1 + x) * (1 + y) * ma
+    return np.array([t0 - cb2 * t1, ab2 * t1 - t2]), abs(t0) + cb2 * abs(t1) + ab2 * abs(t1) + abs(t2)
+
+
+def _polish(g, x, y):
+    """Up to six Newton steps on both conics, each taken only while it lowers |F0| + |F1|
+    -> (x, y, whether the point ends on both conics to 1e-12 of the terms)."""
+    ma, mb, mg, cb2, ab2 = g
+    F, size = _conic_residual(g, x, y)
+    best, cx, cy = np.abs(F).sum(), x, y
+    on = best <= 1e-12 * size
+    for _ in range(6):
+        j00, j01 = 2 * (cx + mg), -2 * cb2 * (cy + mb)
+        j10 = -2 * ((cx - cy) + (1 + cy) * ma)
+        j11 = 2 * ab2 * (cy + mb) - 2 * ((cy - cx) + (1 + cx) * ma)
+        det = j00 * j11 - j01 * j10
+        if not abs(det) > 0:
+            break
+        cx, cy = cx - (F[0] * j11 - F[1] * j01) / det, cy - (F[1] * j00 - F[0] * j10) / det
+        F, size = _conic_residual(g, cx, cy)
+        if not np.abs(F).sum() < best:
+            break
+        best, x, y = np.abs(F).sum(), cx, cy
+        on = best <= 1e-12 * size
+    return x, y, on
+
+
 def p3p(P, f, K=None, uv=None, tol_px=1e-3):
-    """Grunert's P3P.  P (3, 3) world points, f (3, 3) unit bearings -> list of float64 4x4
-    world-in-camera poses with three positive depths.  With K and uv a root is kept only if it
-    reprojects its own three points within tol_px (the device's acceptance rule)."""
+    """Grunert's P3P as csrc/picp_p3p.h has it (numpy.roots in place of the bisection).  P (3, 3)
+    world points, f (3, 3) unit bearings -> list of at most four float64 4x4 world-in-camera poses
+    with three positive depths.  The quartic is in y = s3/s1 - 1, built from 1 - cos of the
+    bearings' angles.  Candidates for y: its real roots and, when fewer than four, its critical
+    points where it all but vanishes (roots of even multiplicity); x = s2/s1 - 1 by the
+    elimination's quotient, or by the first conic where the quotient's denominator is small; every
+    (x, y) polished on both conics and kept only if it ends on them; copies dropped.  With K and uv
+    a root is kept only if it reprojects its own three points within tol_px (the device's rule)."""
     P = np.asarray(P, np.float64)
     f = np.asarray(f, np.float64)
     if not (np.all(np.isfinite(P)) and np.all(np.isfinite(f))):
@@ -68,43 +105,62 @@ def p3p(P, f, K=None, uv=None, tol_px=1e-3):
     nrm = np.cross(P[1] - P[0], P[2] - P[0])
     if not (a2 > 0 and b2 > 0 and c2 > 0 and nrm @ nrm > 1e-10 * b2 * c2):
         return []
-    ca, cb, cg = f[1] @ f[2], f[0] @ f[2], f[0] @ f[1]
-    q, r = (a2 - c2) / b2, (a2 + c2) / b2
-    cb2, ab2 = c2 / b2, a2 / b2
-    A4 = (q - 1) ** 2 - 4 * cb2 * ca ** 2
-    A3 = 4 * (q * (1 - q) * cb - (1 - r) * ca * cg + 2 * cb2 * ca ** 2 * cb)
-    A2 = 2 * (q ** 2 - 1 + 2 * q ** 2 * cb ** 2 + 2 * ((b2 - c2) / b2) * ca ** 2 - 4 * r * ca * cb * cg
-              + 2 * ((b2 - a2) / b2) * cg ** 2)
-    A1 = 4 * (-q * (1 + q) * cb + 2 * ab2 * cg ** 2 * cb - (1 - r) * ca * cg)
-    A0 = (1 + q) ** 2 - 4 * ab2 * cg ** 2
-    coef = np.array([A4, A3, A2, A1, A0])
+    ma, mb, mg = (0.5 * np.sum((f[i] - f[j]) ** 2) for i, j in ((1, 2), (0, 2), (0, 1)))
+    cb2, ab2, q = c2 / b2, a2 / b2, (a2 - c2) / b2
+    g = (ma, mb, mg, cb2, ab2)
+    # descending in y, as numpy has polynomials
+    D = np.array([1 - ma, mg - ma])
+    N = np.array([q - 1, 2 * (q * mb - ma), 2 * ((mg - ma) + q * mb)])
+    c0 = np.array([-cb2, -2 * cb2 * mb, 2 * (mg - cb2 * mb)])
+    coef = np.polyadd(np.polysub(np.polymul(N, N), 4 * mg * np.polymul(N, D)), 4 * np.polymul(np.polymul(D, D), c0))
+    coef = np.concatenate([np.zeros(5 - len(coef)), coef])
     if not np.all(np.isfinite(coef)) or not np.any(coef[:-1] != 0):
         return []
-    out = []
+
+    def real(roots):
+        return sorted(z.real for z in roots if abs(z.imag) <= 1e-9 * max(1.0, abs(z.real)))
+
+    ys = real(np.roots(coef))
+    if len(ys) < 4:
+        for c in real(np.roots(np.polyder(coef))):
+            if abs(np.polyval(coef, c)) <= 1e-12 * np.polyval(np.abs(coef), abs(c)):
+                ys.append(c)
+    out, kept = [], []
     Pc = P.mean(0)
     W = _triad(P[0], P[1], P[2])
-    for root in np.roots(coef):
-        if abs(root.imag) > 1e-9 * max(1.0, abs(root.real)) or not root.real > 0:
+    for y0 in ys:
+        if not y0 > -1:
             continue
-        v = root.real
-        den = cg - v * ca
-        if abs(den) < 1e-9:
-            continue
-        u = ((q - 1) * v * v - 2 * q * cb * v + 1 + q) / (2 * den)
-        d1 = 1 + v * v - 2 * v * cb
-        if not (u > 0 and d1 > 0):
-            continue
-        s1 = np.sqrt(b2 / d1)
-        Q = np.array([s1, u * s1, v * s1])[:, None] * f
-        R = _triad(Q[0], Q[1], Q[2]) @ W.T
-        T = np.eye(4)
-        T[:3, :3] = R
-        T[:3, 3] = Q.mean(0) - R @ Pc
-        if not np.all(np.isfinite(T)):
-            continue
-        if K is not None and reproj_err(T, K, P, uv).max() > tol_px:
-            continue
-        out.append(T)
+        den = D[1] + D[0] * y0
+        if abs(den) >= 1e-4 * (abs(D[1]) + abs(D[0] * y0)):
+            xs = [-np.polyval(N, y0) / (2 * den)]
+        else:
+            cy = np.polyval(c0, y0)
+            disc = mg * mg - cy
+            sq = np.sqrt(max(disc, 0.0))
+            xs = [] if not disc >= -1e-9 * (mg * mg + abs(cy)) else [-mg + sq, -mg - sq] if sq > 0 else [-mg + sq]
+        for x in xs:
+            if len(out) == 4:
+                break
+            x, y, on = _polish(g, x, y0)
+            u, v = 1 + x, 1 + y
+            d1 = y * y + 2 * v * mb
+            if not (on and u > 0 and v > 0 and d1 > 0):
+                continue
+            if any(abs(x - xk) + abs(y - yk) <= 1e-6 * (abs(x) + abs(y) + ma + mb + mg) for xk, yk in kept):
+                continue
+            s1 = np.sqrt(b2 / d1)
+            Q = np.array([s1, u * s1, v * s1])[:, None] * f
+            R = _triad(Q[0], Q[1], Q[2]) @ W.T
+            T = np.eye(4)
+            T[:3, :3] = R
+            T[:3, 3] = Q.mean(0) - R @ Pc
+            if not np.all(np.isfinite(T)):
+                continue
+            if K is not None and reproj_err(T, K, P, uv).max() > tol_px:
+                continue
+            out.append(T)
+            kept.append((x, y))
     return out
 
 

@@ -3,12 +3,26 @@
 // essential unit's) for every polynomial of degree <= 4.  Random coefficients over many scales,
 // polynomials built from chosen roots (repeated, close, zero), vanishing leading coefficients and
 // non-finite entries.  Prints the number of cases and of mismatches; exit status 1 on a mismatch.
+//
+//   poly_check --roots FILE
+//
+// reads one polynomial per line of FILE (coefficients ascending, degree <= 10, decimal or hex
+// floats) and prints per line "d n r_1 .. r_n" for real_roots, where d <= 4 "| n r_1 .. r_n" for
+// real_roots_t<4>, and for a quartic a third such group for p3p_quartic_roots (picp_p3p.h: a copy
+// of the loop's last level between critical points it takes from real_roots_t<4> on the
+// derivative; those come from a call with its own root bound, so its roots are not held to the
+// other two's bits), roots as hex floats: tests/test_pnp_cpu.py compares them with known roots.
 #define PICP_POLY_HOST
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <sstream>
+#include <string>
+#include <vector>
 
+#include "picp_p3p.h"
 #include "picp_poly.h"
 
 static uint64_t g_state = 0x243F6A8885A308D3ull;
@@ -45,7 +59,53 @@ static void from_roots(const double* r, int n, double lead, double* p) {
   }
 }
 
-int main() {
+static int print_roots(const char* path) {
+  std::FILE* fp = std::fopen(path, "r");
+  if (!fp) {
+    std::fprintf(stderr, "poly_check: cannot open %s\n", path);
+    return 2;
+  }
+  char line[4096];
+  while (std::fgets(line, sizeof line, fp)) {
+    std::istringstream in(line);
+    std::vector<double> c;
+    std::string tok;
+    while (in >> tok) c.push_back(std::strtod(tok.c_str(), nullptr));
+    if (c.empty()) continue;
+    if (c.size() > 11) {
+      std::fprintf(stderr, "poly_check: degree above 10\n");
+      std::fclose(fp);
+      return 2;
+    }
+    const int d = (int)c.size() - 1;
+    double a[10], b[4];
+    const int na = real_roots(c.data(), d, a);
+    std::printf("%d %d", d, na);
+    for (int k = 0; k < na; ++k) std::printf(" %a", a[k]);
+    if (d <= 4) {
+      const int nb = real_roots_t<4>(c.data(), d, b);
+      std::printf(" | %d", nb);
+      for (int k = 0; k < nb; ++k) std::printf(" %a", b[k]);
+    }
+    if (d == 4 && c[4] != 0.0) {
+      double crit[4];
+      int nc = 0;
+      const int nq = p3p_quartic_roots(c.data(), b, crit, &nc);
+      std::printf(" | %d", nq);
+      for (int k = 0; k < nq; ++k) std::printf(" %a", b[k]);
+    }
+    std::printf("\n");
+  }
+  std::fclose(fp);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 3 && std::strcmp(argv[1], "--roots") == 0) return print_roots(argv[2]);
+  if (argc != 1) {
+    std::fprintf(stderr, "usage: poly_check [--roots FILE]\n");
+    return 2;
+  }
   double p[5];
   for (int it = 0; it < 200000; ++it) {
     const int d = 1 + (int)(next64() % 4);
