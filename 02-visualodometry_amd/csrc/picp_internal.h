@@ -175,6 +175,34 @@ struct PnpItems {
   const int64_t* base;
 };
 
+// 3D-3D alignment by Sim(3) RANSAC (picp_sim3.hip), by value
+struct Sim3Args {
+  float threshold;       // squared distance in dst units, strict
+  int32_t with_scale;    // 0: rigid, c = 1
+  uint64_t seed;
+  int32_t n_problems;
+  int32_t hyp;           // hypotheses per problem
+  int32_t min_inliers;
+  int32_t refits;
+  int32_t prob0;         // batch position of problem 0 (the sampling function's problem index)
+  int32_t fit_only;      // the refit kernel alone over a given set (picp_sim3_fit_batch)
+};
+
+// The pairs of a Sim(3) batch: packed float3 (x = src, y = src + 1, z = src + 2, stride 3) or any
+// other element stride.  Pair j of problem i is element base[i] + j of both sets; offs
+// (n_problems + 1) gives the sizes and the position of the problem's mask bytes.
+struct Sim3Items {
+  const float* px;
+  const float* py;
+  const float* pz;
+  const float* qx;
+  const float* qy;
+  const float* qz;
+  int32_t sp, sq;        // element strides of the src and of the dst coordinates
+  const int64_t* offs;
+  const int64_t* base;
+};
+
 // ---------------------------------------------------------------------------------------
 // device-resident VO sequence (picp_vo.hip; VoSegment: picp_problem.h)
 struct VoStep {     // per pose slot; slot 0 of a segment = the bootstrap

@@ -112,6 +112,38 @@ hipError_t picp_launch_pnp_select(hipStream_t stream, const PnpArgs* A, const Pn
                                   const float* hyp_T, const int32_t* cnt, float* T_out, int32_t* inliers,
                                   int32_t* found, uint8_t* mask);
 
+// ---- picp_sim3.hip
+// Per-(problem, hypothesis) arrays are indexed p * hyp + h: samples 3, hyp_valid 1, hyp_S 16 floats
+// (M = c R column-major, t, c, 3 unused), cnt 1 (zeroed by the caller before the score launch).
+int picp_sim3_score_tile(void);  // pairs one score block holds
+int picp_sim3_hyp_tile(void);    // hypotheses per count tile (a slice of the score grid's y takes whole tiles)
+hipError_t picp_launch_sim3_samples(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, int32_t* samples);
+hipError_t picp_launch_sim3_hyp(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, const int32_t* samples,
+                                int32_t* hyp_valid, float* hyp_S);
+// blk[nb]: (problem, first pair) of every score block; hsplit: hypothesis slices (grid y)
+hipError_t picp_launch_sim3_score(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, int nb, const int2* blk,
+                                  int hsplit, const int32_t* hyp_valid, const float* hyp_S, int32_t* cnt);
+hipError_t picp_launch_sim3_select(hipStream_t stream, const Sim3Args* A, const int32_t* hyp_valid, const int32_t* cnt,
+                                   int32_t* win);
+// refit_S (refits x 16 floats per problem, as hyp_S), refit_count, scale, inliers, rms and mask
+// (indexed offs[p] + j) are nullable; with A->fit_only, win and hyp_S are not read and fit_mask
+// (nullable, indexed offs[p] + j) selects the pairs
+hipError_t picp_launch_sim3_refit(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, const int32_t* win,
+                                  const float* hyp_S, const uint8_t* fit_mask, float* refit_S, int32_t* refit_count,
+                                  float* S_out, float* scale, int32_t* inliers, int32_t* found, float* rms,
+                                  uint8_t* mask);
+
+// the glue of picp_vo_align_segments: the match problems (segment s + 1's map against segment s's)
+// from the map counts, the accepted queries per problem, and the pairs (packed float3) in ascending
+// query index at offs[s] (offs: the prefix sums of n_pairs)
+hipError_t picp_launch_vo_align_probs(hipStream_t stream, const VoSegment* segs, const int64_t* map_n, int n_problems,
+                                      MatchProblem* probs);
+hipError_t picp_launch_vo_align_count(hipStream_t stream, const MatchProblem* probs, int n_problems,
+                                      const int32_t* accepted, int64_t* n_pairs);
+hipError_t picp_launch_vo_align_pairs(hipStream_t stream, const MatchProblem* probs, int n_problems,
+                                      const int32_t* accepted, const int32_t* best, const float* map_xyz,
+                                      const int64_t* offs, float* src, float* dst);
+
 // ---- picp_match.hip
 hipError_t picp_launch_match(hipStream_t stream, int n_problems, int64_t max_nq, const float* q_desc,
                              const float* r_desc, const MatchProblem* probs, int dim, float dist_thr,

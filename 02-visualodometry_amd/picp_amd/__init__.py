@@ -58,6 +58,8 @@ EXPORTED = [
     "picp_refine_get_poses", "picp_refine_get_pose_stats", "picp_refine_get_pose_view", "picp_refine_get_sweeps",
     "picp_refine_adjust_time", "picp_vo_adjust", "picp_vo_get_adjusted_poses_wc", "picp_vo_get_adjusted_map",
     "picp_pnp_params_default", "picp_pnp_batch", "picp_pnp_batch_debug", "picp_pnp_batch_time", "picp_relocalize",
+    "picp_sim3_params_default", "picp_sim3_batch", "picp_sim3_batch_debug", "picp_sim3_batch_time", "picp_sim3_fit_batch",
+    "picp_vo_align_segments",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -111,6 +113,13 @@ class PnpParams(ctypes.Structure):
     """picp_pnp_params (include/picp_c.h): the P3P RANSAC's gate, hypothesis count and seed."""
     _fields_ = [("threshold", ctypes.c_float), ("hypotheses", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+class Sim3Params(ctypes.Structure):
+    """picp_sim3_params (include/picp_c.h): the Sim(3) RANSAC's gate, hypothesis count, refits and seed."""
+    _fields_ = [("threshold", ctypes.c_float), ("hypotheses", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("with_scale", ctypes.c_int32), ("refits", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
 
 
 _lib = None
@@ -244,6 +253,13 @@ def lib():
                                   u8p, i32p, i32p, fp, i32p], i),
         "picp_pnp_batch_time": ([i, i, ctypes.POINTER(i64), fp, fp, fp, i, i, ctypes.POINTER(PnpParams), i, fp], i),
         "picp_relocalize": ([vp, ctypes.POINTER(PnpParams), i32p], i),
+        "picp_sim3_params_default": ([ctypes.POINTER(Sim3Params)], None),
+        "picp_sim3_batch": ([i, i, ctypes.POINTER(i64), fp, fp, ctypes.POINTER(Sim3Params), fp, fp, i32p, i32p, fp, u8p], i),
+        "picp_sim3_batch_debug": ([i, i, ctypes.POINTER(i64), fp, fp, ctypes.POINTER(Sim3Params), fp, fp, i32p, i32p, fp,
+                                   u8p, i32p, i32p, fp, i32p, fp, i32p], i),
+        "picp_sim3_batch_time": ([i, i, ctypes.POINTER(i64), fp, fp, ctypes.POINTER(Sim3Params), i, fp], i),
+        "picp_sim3_fit_batch": ([i, i, ctypes.POINTER(i64), fp, fp, u8p, i, fp, fp, fp, i32p], i),
+        "picp_vo_align_segments": ([vp, ctypes.POINTER(Sim3Params), fp, fp, i32p, i32p, ctypes.POINTER(i64)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -800,6 +816,111 @@ def pnp_ransac_time(xyz_list, uv_list, reps, K=None, rows=480, cols=640, thresho
     return tuple(float(x) for x in us)
 
 
+def _sim3_pack(src_list, dst_list):
+    offs = np.zeros(len(src_list) + 1, np.int64)
+    offs[1:] = np.cumsum([len(x) for x in src_list])
+    n = int(offs[-1])
+    pack = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L])
+                                          if n else np.zeros((0, 3), np.float32))
+    src, dst = pack(src_list), pack(dst_list)
+    assert len(src) == len(dst) == n and all(len(a) == len(b) for a, b in zip(src_list, dst_list))
+    return offs, src, dst
+
+
+def default_sim3_params(**kw):
+    p = Sim3Params()
+    lib().picp_sim3_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def sim3_ransac_batch(src_list, dst_list, threshold=0.01, hypotheses=256, min_inliers=4, with_scale=True, refits=2,
+                      seed=0, want_mask=False, debug=False, device=0):
+    """picp_sim3_batch: the similarity dst ~ c R src + t of many sets of 3D-3D matches, robust to wrong
+    ones (Umeyama's closed form inside RANSAC, then `refits` least-squares refits of the inliers;
+    `threshold` is a squared distance in dst units).  Returns per problem a dict with S (4x4
+    [[c R, t], [0, 1]]; the identity when found is False), scale, inliers, found, rms (and mask);
+    with debug also samples (H, 3), hyp_valid (H,), hyp_S (H, 4, 4), hyp_count (H,), refit_S
+    (refits, 4, 4) and refit_count (refits,)."""
+    P = len(src_list)
+    offs, src, dst = _sim3_pack(src_list, dst_list)
+    n, H = int(offs[-1]), hypotheses
+    prm = Sim3Params(threshold, hypotheses, min_inliers, 1 if with_scale else 0, refits, 0, seed)
+    S = np.zeros(16 * max(P, 1), np.float32)
+    scale = np.zeros(max(P, 1), np.float32)
+    inl = np.zeros(max(P, 1), np.int32)
+    found = np.zeros(max(P, 1), np.int32)
+    rms = np.zeros(max(P, 1), np.float32)
+    mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+    u8 = ctypes.POINTER(ctypes.c_uint8)
+    args = [device, P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _fptr(src) if n else None,
+            _fptr(dst) if n else None, ctypes.byref(prm), _fptr(S), _fptr(scale), _i32ptr(inl), _i32ptr(found),
+            _fptr(rms), mask.ctypes.data_as(u8) if want_mask else None]
+    if debug:
+        G, NR = max(P * max(H, 0), 1), max(P * max(refits, 0), 1)
+        smp = np.zeros(3 * G, np.int32)
+        hv = np.zeros(G, np.int32)
+        hS = np.zeros(16 * G, np.float32)
+        hc = np.zeros(G, np.int32)
+        rS = np.zeros(16 * NR, np.float32)
+        rc = np.zeros(NR, np.int32)
+        _check(lib().picp_sim3_batch_debug(*args, _i32ptr(smp), _i32ptr(hv), _fptr(hS), _i32ptr(hc), _fptr(rS),
+                                           _i32ptr(rc)))
+    else:
+        _check(lib().picp_sim3_batch(*args))
+    out = []
+    for i in range(P):
+        d = {"S": pose_from_c(S[16 * i:16 * i + 16]), "scale": float(scale[i]), "inliers": int(inl[i]),
+             "found": bool(found[i]), "rms": float(rms[i])}
+        if want_mask:
+            d["mask"] = mask[offs[i]:offs[i + 1]].astype(bool)
+        if debug:
+            g, r = slice(i * H, (i + 1) * H), slice(i * refits, (i + 1) * refits)
+            d["samples"] = smp.reshape(-1, 3)[g]
+            d["hyp_valid"] = hv[g]
+            d["hyp_S"] = np.transpose(hS.reshape(-1, 4, 4)[g], (0, 2, 1)).copy()
+            d["hyp_count"] = hc[g]
+            d["refit_S"] = np.transpose(rS.reshape(-1, 4, 4)[r], (0, 2, 1)).copy()
+            d["refit_count"] = rc[r]
+        out.append(d)
+    return out
+
+
+def sim3_fit_batch(src_list, dst_list, mask_list=None, with_scale=True, device=0):
+    """picp_sim3_fit_batch: the least-squares similarity of every finite pair (of those whose mask
+    entry is set), one per problem -> list of dict(S, scale, rms, found)."""
+    P = len(src_list)
+    offs, src, dst = _sim3_pack(src_list, dst_list)
+    n = int(offs[-1])
+    mask = None
+    if mask_list is not None:
+        mask = np.ascontiguousarray(np.concatenate([np.asarray(m).astype(np.uint8).reshape(-1) for m in mask_list])
+                                    if n else np.zeros(0, np.uint8))
+        assert len(mask) == n
+    S = np.zeros(16 * max(P, 1), np.float32)
+    scale = np.zeros(max(P, 1), np.float32)
+    rms = np.zeros(max(P, 1), np.float32)
+    found = np.zeros(max(P, 1), np.int32)
+    _check(lib().picp_sim3_fit_batch(device, P, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                     _fptr(src) if n else None, _fptr(dst) if n else None,
+                                     mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None and n else None,
+                                     1 if with_scale else 0, _fptr(S), _fptr(scale), _fptr(rms), _i32ptr(found)))
+    return [{"S": pose_from_c(S[16 * i:16 * i + 16]), "scale": float(scale[i]), "rms": float(rms[i]),
+             "found": bool(found[i])} for i in range(P)]
+
+
+def sim3_ransac_time(src_list, dst_list, reps, threshold=0.01, hypotheses=256, with_scale=True, refits=2, seed=0,
+                     device=0):
+    """picp_sim3_batch_time: mean device time in us of the (samples, hypotheses, score, select, refit) stages."""
+    offs, src, dst = _sim3_pack(src_list, dst_list)
+    prm = Sim3Params(threshold, hypotheses, 4, 1 if with_scale else 0, refits, 0, seed)
+    us = np.zeros(5, np.float32)
+    _check(lib().picp_sim3_batch_time(device, len(src_list), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                      _fptr(src), _fptr(dst), ctypes.byref(prm), reps, _fptr(us)))
+    return tuple(float(x) for x in us)
+
+
 class VOSequence:
     """Device-resident VO over a packed observation sequence (C-ABI picp_vo_*): the reference's
     per-frame loop (exec/icp_test.cpp:61-136) run on the GPU for independent segments in
@@ -970,6 +1091,23 @@ class VOSequence:
         st = (Stats * max(n.value, 1))()
         _check(lib().picp_vo_get_adjusted_map(self._h, seg, n.value, _fptr(xyz), st, ctypes.byref(n)))
         return xyz[:n.value], _stats_arrays(st, n.value)
+
+    def align_segments(self, **params):
+        """picp_vo_align_segments: consecutive segments aligned through their shared landmarks
+        (segment s + 1's map matched against segment s's on the device, then the Sim(3) RANSAC with
+        `params`: Sim3Params' fields).  Returns one dict per s < n_seg - 1: S (4x4, maps segment
+        s + 1's frame into segment s's), scale, inliers, found, n_pairs.  Reads the run only."""
+        prm = default_sim3_params(**params)
+        P = max(len(self.steps) - 1, 0) if self.steps is not None else 0
+        S = np.zeros(16 * max(P, 1), np.float32)
+        scale = np.zeros(max(P, 1), np.float32)
+        inl = np.zeros(max(P, 1), np.int32)
+        found = np.zeros(max(P, 1), np.int32)
+        npairs = np.zeros(max(P, 1), np.int64)
+        _check(lib().picp_vo_align_segments(self._h, ctypes.byref(prm), _fptr(S), _fptr(scale), _i32ptr(inl),
+                                            _i32ptr(found), npairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return [{"S": pose_from_c(S[16 * s:16 * s + 16]), "scale": float(scale[s]), "inliers": int(inl[s]),
+                 "found": bool(found[s]), "n_pairs": int(npairs[s])} for s in range(P)]
 
     def map(self, seg):
         n = ctypes.c_int64()

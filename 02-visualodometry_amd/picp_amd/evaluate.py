@@ -39,6 +39,15 @@ def umeyama(src, dst, with_scale=True):
     return T
 
 
+def chain_similarities(S_list):
+    """S_list[s] maps segment s + 1's frame into segment s's (VOSequence.align_segments).  Returns
+    the float64 products into segment 0's frame: out[0] = I, out[s + 1] = out[s] @ S_list[s]."""
+    out = [np.eye(4)]
+    for S in S_list:
+        out.append(out[-1] @ np.asarray(S, np.float64))
+    return out
+
+
 def _rot_angle(R):
     return float(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
 

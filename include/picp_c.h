@@ -621,6 +621,97 @@ int picp_pnp_batch_time(int device, int n_problems, const int64_t* offs, const f
  * either way.  Follow with picp_solve. */
 int picp_relocalize(picp_t* h, const picp_pnp_params* prm, int32_t* inliers);
 
+/* ---------------- 3D-3D alignment: Sim(3) RANSAC ---------------- */
+/* "Here are 3D-3D matches between two point sets, which scale, rotation and translation map one
+ * onto the other?" (map to map, map to a surveyed reference, a revisited place to its first
+ * visit), robust to wrong matches: Umeyama's closed form on three pairs inside RANSAC, every
+ * hypothesis scored, then local optimisation (the least-squares transform of the inliers, `refits`
+ * times).  Problems are ragged: problem i owns pairs [offs[i], offs[i+1]) of src and dst (3 floats
+ * each); offs[0] = 0.  The transform is dst ~ M src + t with M = c R, c > 0, det R = +1.
+ *
+ * The samples are those of picp_pnp_batch: hypothesis h of problem i with n >= 4 pairs draws the
+ * triple (a, b, c) of (seed, i, h, n) stated there.  Its transform is the closed form of the three
+ * pairs, computed in double and rounded to float32; that float32 transform is the one scored.  A
+ * triple gives no transform (and is never the winner) when a coordinate is not finite or the
+ * three points of either set coincide or lie on a line (sigma_2 <= 1e-10 sigma_1 of their
+ * covariance).
+ *
+ * The inlier test, in float32 without contraction, with m_rc the element of M in row r, column c,
+ * p = (x, y, z) the src point and q the dst point, per row r:
+ *   e_r = (((m_r0 * x + m_r1 * y) + m_r2 * z) + t_r) - q_r
+ *   d2 = (e_0 * e_0 + e_1 * e_1) + e_2 * e_2
+ * The pair is an inlier iff d2 < threshold (strict: a NaN fails).
+ *
+ * The winner is the valid hypothesis with the largest count, then the lowest index: candidate 0.
+ * Refit r = 1..refits is the least-squares transform (in double, rounded to float32) of the
+ * inliers of candidate r - 1, its count taken by the test above; a refit that gives no transform
+ * (fewer than 3 inliers, rank < 2) ends the chain.  The moments are summed about the inlier of
+ * the lowest index, so a cloud far from the origin keeps its digits.  The result is the
+ * candidate with the largest count, the latest on a tie (a refit that keeps the count is the
+ * least-squares transform of as many inliers, where the winner is a three-point guess).
+ *
+ * found[i] = 1 when n >= 4, some hypothesis is valid and the result's count >= min_inliers:
+ * S_out (16 floats, column-major 4x4 [[c R, t], [0, 1]]) is the result, scale[i] its c, inliers[i]
+ * its count, rms[i] the root mean square distance of its inliers, mask (one byte per pair) its
+ * inliers.  Otherwise found[i] = 0, S_out is the identity, scale 1, rms 0, the mask all 0 and
+ * inliers[i] the best count seen (0 when no hypothesis is valid).  scale, rms and mask are
+ * nullable.  The same inputs give the same bits on every call.  n_problems * hypotheses is
+ * limited to 2^24 per call. */
+typedef struct picp_sim3_params {
+  float threshold;      /* squared distance in dst units, strict; default 0.01 */
+  int32_t hypotheses;   /* per problem, default 256, 1..65536 */
+  int32_t min_inliers;  /* default 4 */
+  int32_t with_scale;   /* default 1; 0: rigid, c = 1 */
+  int32_t refits;       /* default 2, 0..8 */
+  int32_t reserved;
+  uint64_t seed;        /* default 0 */
+} picp_sim3_params;
+
+void picp_sim3_params_default(picp_sim3_params* p);
+
+/* prm NULL = picp_sim3_params_default.  n_problems == 0 returns PICP_OK. */
+int picp_sim3_batch(int device, int n_problems, const int64_t* offs, const float* src, const float* dst,
+                    const picp_sim3_params* prm, float* S_out, float* scale, int32_t* inliers, int32_t* found,
+                    float* rms, uint8_t* mask);
+
+/* picp_sim3_batch with the intermediate arrays, for tests; every output pointer may be NULL.  With
+ * H = hypotheses, per problem: samples 3 H indices, hyp_valid H, hyp_S H x 16 floats (column-major
+ * 4x4; zero where not valid), hyp_count H, refit_S refits x 16 (zero where the chain has ended),
+ * refit_count refits (-1 where the chain has ended). */
+int picp_sim3_batch_debug(int device, int n_problems, const int64_t* offs, const float* src, const float* dst,
+                          const picp_sim3_params* prm, float* S_out, float* scale, int32_t* inliers,
+                          int32_t* found, float* rms, uint8_t* mask, int32_t* samples, int32_t* hyp_valid,
+                          float* hyp_S, int32_t* hyp_count, float* refit_S, int32_t* refit_count);
+
+/* mean device time in us of the five stages (samples, hypotheses, score, select, refit) over
+ * `reps` repetitions after one untimed pass; us[5] */
+int picp_sim3_batch_time(int device, int n_problems, const int64_t* offs, const float* src, const float* dst,
+                         const picp_sim3_params* prm, int reps, float* us);
+
+/* The refit stage alone (the device counterpart of a least-squares alignment of two trajectories):
+ * per problem the transform of all pairs whose six coordinates are finite, or with mask (one byte
+ * per pair, nullable) of those among them whose byte is not 0; the same sums in the same order as
+ * a refit over that set.  found[i] = 0 (S_out the identity, scale 1, rms 0) when the set gives no
+ * transform.  scale and rms are nullable. */
+int picp_sim3_fit_batch(int device, int n_problems, const int64_t* offs, const float* src, const float* dst,
+                        const uint8_t* mask, int with_scale, float* S_out, float* scale, float* rms,
+                        int32_t* found);
+
+/* The first user: consecutive segments of a device-resident VO run, each in a world frame and
+ * scale of its own, aligned through their shared landmarks.  For every s < n_seg - 1, problem s
+ * is built on the device: segment s + 1's map descriptors are the queries and segment s's the
+ * references of the matcher's full form at the sequence's thresholds (0.2 / 0.8), and the accepted
+ * queries j, in ascending index, give the pairs src = xyz_{s+1}[j], dst = xyz_s[best[j]].  The
+ * problems then run as picp_sim3_batch runs them (problem s at batch position s), and the outputs
+ * have the bits of that call on the same pairs built on the host from picp_vo_get_map and
+ * picp_match_batch: S_out[s] ((n_seg - 1) x 16) maps segment s + 1's frame into segment s's.
+ * Blocking and read-only: the run's maps, poses and step records, and any later call, keep their
+ * bits; the host reads back only the pair counts.  The state conditions are picp_vo_get_map's.
+ * scale and n_pairs (the accepted matches per problem) are nullable.  One segment: nothing to do,
+ * PICP_OK. */
+int picp_vo_align_segments(picp_vo_t* h, const picp_sim3_params* prm, float* S_out, float* scale, int32_t* inliers,
+                           int32_t* found, int64_t* n_pairs);
+
 /* ---------------- self-test ---------------- */
 /* The projection's reciprocal 1/z must be the correctly rounded one (src/camera.h:30; the
  * chi2 gate is bit-exact): the kernels use a 3-instruction form, valid for every float in
