@@ -329,17 +329,14 @@ int batch_create(picp_batch** out, int device, int np, const int64_t* offs, int 
                         int cols, const float K[9]) {
   CHECK_ARG(out && offs && K, "picp_batch_create: null argument");
   CHECK_ARG(rows > 0 && cols > 0, "picp_batch_create: rows/cols must be positive");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_batch_create: no such HIP device");
+  if (int rc = select_device("picp_batch_create", device)) return rc;
   picp_batch* b = new picp_batch();
   b->device = device;
   b->rows = rows;
   b->cols = cols;
   memcpy(b->K, K, sizeof(b->K));
   picp_params_default(&b->params);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&b->num_cu, hipDeviceAttributeMultiprocessorCount, device);
+  hipError_t e = hipDeviceGetAttribute(&b->num_cu, hipDeviceAttributeMultiprocessorCount, device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
   if (const char* t = getenv("PICP_TIMEOUT_MS")) b->timeout_ticks = (unsigned long long)(atof(t) * 1e5);
   if (e != hipSuccess) {

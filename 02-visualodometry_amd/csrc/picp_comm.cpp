@@ -128,11 +128,8 @@ extern "C" int picp_comm_create(picp_comm_t** out, int device, int world, int ra
                                 const uint8_t id[PICP_COMM_ID_BYTES]) {
   CHECK_ARG(out && id, "picp_comm_create: null argument");
   CHECK_ARG(world >= 1 && rank >= 0 && rank < world, "picp_comm_create: bad world/rank");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_comm_create: no such HIP device");
+  if (int rc = select_device("picp_comm_create", device)) return rc;
   RCCL_API_OR_FAIL();
-  HIP_TRY(hipSetDevice(device));
   picp_comm* c = new picp_comm();
   c->device = device;
   c->world = world;

@@ -12,6 +12,7 @@
 #include "picp_c.h"
 #include "picp_host.h"
 #include "picp_launch.h"
+#include "picp_ransac_host.h"
 
 #define set_err picp_set_err
 
@@ -48,10 +49,7 @@ extern "C" int picp_triangulate(int device, const float P1[12], const float P2[1
   CHECK_ARG(P1 && P2, "picp_triangulate: null projection matrix");
   CHECK_ARG(q >= 0 && (q == 0 || (uv1 && uv2 && xyz)), "picp_triangulate: bad arrays");
   if (q == 0) return PICP_OK;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_triangulate: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = select_device("picp_triangulate", device)) return rc;
   const size_t bytes = 2 * 12 * sizeof(float) + (size_t)q * (2 + 2 + 3) * sizeof(float);
   char* buf = nullptr;
   HIP_TRY(hipMalloc(&buf, bytes));
@@ -85,21 +83,15 @@ extern "C" int picp_essential_batch(int device, int n_problems, const int64_t* o
                                     const float* p2, const float K[9], const picp_essential_params* prm,
                                     float* T_out, int32_t* inliers, int32_t* good, uint8_t* mask) {
   CHECK_ARG(n_problems >= 1 && offs && K && T_out && inliers && good, "picp_essential_batch: null argument");
-  CHECK_ARG(offs[0] == 0, "picp_essential_batch: offsets must start at 0");
-  for (int i = 0; i < n_problems; ++i)
-    CHECK_ARG(offs[i + 1] >= offs[i] && offs[i + 1] - offs[i] <= INT32_MAX, "picp_essential_batch: bad offsets");
+  if (int rc = check_ragged_batch("picp_essential_batch", n_problems, offs, p1, p2)) return rc;
   const int64_t total = offs[n_problems];
-  CHECK_ARG(total == 0 || (p1 && p2), "picp_essential_batch: null points");
   picp_essential_params dp;
   picp_essential_params_default(&dp);
   const picp_essential_params& P = prm ? *prm : dp;
   CHECK_ARG(P.max_iters >= 1 && P.max_iters <= 100000, "picp_essential_batch: max_iters out of range");
   CHECK_ARG(P.threshold > 0.0 && P.prob > 0.0 && P.prob < 1.0 && P.dist > 0.0, "picp_essential_batch: bad params");
   CHECK_ARG(K[0] != 0.0f && K[4] != 0.0f, "picp_essential_batch: K has a zero focal length");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_essential_batch: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = select_device("picp_essential_batch", device)) return rc;
   EssArgs A;
   memset(&A, 0, sizeof(A));
   A.n_problems = n_problems;
@@ -180,10 +172,7 @@ extern "C" int picp_match_batch_form(int device, int n_problems, const int64_t* 
   CHECK_ARG((n1 == 0 || (desc1 && best_idx && best_dist && second_dist && accepted)) && (n2 == 0 || desc2),
             "picp_match_batch: null array");
   if (n1 == 0) return PICP_OK;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_match_batch: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = select_device("picp_match_batch", device)) return rc;
   std::vector<MatchProblem> probs((size_t)n_problems);
   int64_t max_nq = 0;
   for (int i = 0; i < n_problems; ++i) {

@@ -21,6 +21,10 @@ using picp::state_to_pose;
 // picp_runtime.cpp
 void state_to_stats(const PicpState& s, picp_stats& st);
 
+// checks that `device` exists (PICP_ERR_ARG, the message names the caller `what`) and makes it the
+// thread's current one.  picp_runtime.cpp
+int select_device(const char* what, int device);
+
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Device buffer *ptr of *cap elements of `elem` bytes, discarded and allocated anew (at least 256

@@ -96,12 +96,16 @@ hipError_t picp_launch_essential(hipStream_t stream, const EssArgs* args, const 
                                  const float* p2, int32_t* idx, double* Es, int32_t* ns, int32_t* cnt,
                                  float* T_out, int32_t* inliers, int32_t* good, uint8_t* mask);
 
+// ---- picp_ransac.hip
+// both RANSAC solvers' samples[3 (p * hyp + h) + k] (zeros where n < 4); prob0: problem 0's batch position
+hipError_t picp_launch_ransac_samples(hipStream_t stream, uint64_t seed, int32_t prob0, int32_t n_problems,
+                                      int32_t hyp, const int64_t* offs, int32_t* samples);
+
 // ---- picp_pnp.hip
 // Per-(problem, hypothesis) arrays are indexed p * hyp + h: samples 3, n_roots 1, hyp_T 4 poses of
 // 12 floats (R column-major, then t), cnt 4 (zeroed by the caller before the score launch).
 int picp_pnp_score_tile(void);  // correspondences one score block holds
 int picp_pnp_hyp_tile(void);    // hypotheses per count tile (a slice of the score grid's y takes whole tiles)
-hipError_t picp_launch_pnp_samples(hipStream_t stream, const PnpArgs* A, const PnpItems* I, int32_t* samples);
 hipError_t picp_launch_pnp_solve(hipStream_t stream, const PnpArgs* A, const PnpItems* I, const int32_t* samples,
                                  int32_t* n_roots, float* hyp_T);
 // blk[nb]: (problem, first correspondence) of every score block; hsplit: hypothesis slices (grid y)
@@ -117,7 +121,6 @@ hipError_t picp_launch_pnp_select(hipStream_t stream, const PnpArgs* A, const Pn
 // (M = c R column-major, t, c, 3 unused), cnt 1 (zeroed by the caller before the score launch).
 int picp_sim3_score_tile(void);  // pairs one score block holds
 int picp_sim3_hyp_tile(void);    // hypotheses per count tile (a slice of the score grid's y takes whole tiles)
-hipError_t picp_launch_sim3_samples(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, int32_t* samples);
 hipError_t picp_launch_sim3_hyp(hipStream_t stream, const Sim3Args* A, const Sim3Items* I, const int32_t* samples,
                                 int32_t* hyp_valid, float* hyp_S);
 // blk[nb]: (problem, first pair) of every score block; hsplit: hypothesis slices (grid y)

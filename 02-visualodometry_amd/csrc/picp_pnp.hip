@@ -1,8 +1,7 @@
 // picp_pnp.hip -- absolute pose without a prior: P3P inside RANSAC for a ragged batch of 2D-3D
 // problems, scored with PICP's own gate (classify_item) and meant to be polished by PICP itself
-// (DESIGN.md §4.12).  Four launches:
-//   1. picp_pnp_samples_kernel  one lane per (problem, hypothesis): three distinct indices, a pure
-//                               counter-based function of (seed, problem, hypothesis) (picp_c.h);
+// (DESIGN.md §4.12).  Four launches; what the Sim(3) solver has too is in picp_ransac.h:
+//   1. picp_ransac_samples_kernel (picp_ransac.hip): three distinct indices per (problem, hypothesis);
 //   2. picp_pnp_solve_kernel    one lane per (problem, hypothesis), in double with contraction off:
 //                               Grunert's quartic (picp_p3p.h), up to four float32 world-in-camera poses;
 //   3. picp_pnp_score_kernel    the hot path: a block keeps up to PNP_TILE correspondences of one
@@ -23,6 +22,7 @@
 #include "picp_launch.h"
 #include "picp_p3p.h"
 #include "picp_pose.h"
+#include "picp_ransac.h"
 #include "picp_variant.h"
 
 #pragma clang fp contract(off)
@@ -37,30 +37,6 @@ namespace {
 using picp::Cam;
 using picp::Pose;
 
-// splitmix64's output function of the state x + golden gamma
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// the sampling function of include/picp_c.h (n >= 3)
-__device__ __forceinline__ void sample_triple(uint64_t seed, uint32_t i, uint32_t h, uint32_t n, int32_t id[3]) {
-  const uint64_t key = mix64(seed ^ mix64(((uint64_t)i << 32) | h));
-  const uint64_t r0 = mix64(key) >> 32, r1 = mix64(key + 1) >> 32, r2 = mix64(key + 2) >> 32;
-  const uint32_t a = (uint32_t)((r0 * n) >> 32);
-  uint32_t b = (uint32_t)((r1 * (n - 1)) >> 32);
-  b += (b >= a) ? 1u : 0u;
-  uint32_t c = (uint32_t)((r2 * (n - 2)) >> 32);
-  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  c += (c >= lo) ? 1u : 0u;
-  c += (c >= hi) ? 1u : 0u;
-  id[0] = (int32_t)a;
-  id[1] = (int32_t)b;
-  id[2] = (int32_t)c;
-}
-
 // whether correspondence j (< n) of the problem at element b is an inlier of pose T
 template <bool PIN>
 __device__ __forceinline__ bool pnp_inlier(const Pose& T, const Cam& C, float thr, float x, float y, float z, float u,
@@ -70,18 +46,6 @@ __device__ __forceinline__ bool pnp_inlier(const Pose& T, const Cam& C, float th
 }
 
 }  // namespace
-
-// 1. the samples of (problem, hypothesis) g = p * hyp + h
-extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_samples_kernel(PnpArgs A, PnpItems I,
-                                                                             int32_t* __restrict__ samples) {
-  const int64_t g = (int64_t)blockIdx.x * PNP_BS + threadIdx.x;
-  if (g >= (int64_t)A.n_problems * A.hyp) return;
-  const int p = (int)(g / A.hyp), h = (int)(g % A.hyp);
-  const int64_t n = I.offs[p + 1] - I.offs[p];
-  int32_t id[3] = {0, 0, 0};
-  if (n >= 4) sample_triple(A.seed, (uint32_t)(A.prob0 + p), (uint32_t)h, (uint32_t)n, id);
-  for (int k = 0; k < 3; ++k) samples[3 * g + k] = id[k];
-}
 
 // 2. the poses of (problem, hypothesis) g
 extern "C" __global__ __launch_bounds__(64) void picp_pnp_solve_kernel(PnpArgs A, PnpItems I,
@@ -182,33 +146,16 @@ extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_select_kernel(
     const int32_t* __restrict__ cnt, float* __restrict__ T_out, int32_t* __restrict__ inliers,
     int32_t* __restrict__ found, uint8_t* __restrict__ mask) {
   __shared__ unsigned long long s_key[PNP_BS / 64];
-  __shared__ unsigned long long s_win;
   const int p = blockIdx.x, tid = threadIdx.x;
   const int n = (int)(I.offs[p + 1] - I.offs[p]);
   const size_t ph0 = (size_t)p * A.hyp;
-  // key of entry e = 4 h + r (r < n_roots[h]): (count + 1) above ~e, so the maximum is the
-  // largest count at the lowest entry and 0 means no entry; it does not depend on who finds it
-  unsigned long long key = 0;
-  for (int64_t e = tid; e < (int64_t)A.hyp * 4; e += PNP_BS) {
-    if ((int)(e & 3) >= n_roots[ph0 + (e >> 2)]) continue;
-    const unsigned long long k = ((unsigned long long)((unsigned)cnt[ph0 * 4 + e] + 1u) << 32) | (unsigned)~(unsigned)e;
-    key = k > key ? k : key;
-  }
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = __shfl_xor(key, m);
-    key = o > key ? o : key;
-  }
-  if ((tid & 63) == 0) s_key[tid >> 6] = key;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < PNP_BS / 64; ++w) key = s_key[w] > key ? s_key[w] : key;
-    s_win = key;
-  }
-  __syncthreads();
-  key = s_win;
-  const int best = key ? (int)(key >> 32) - 1 : 0;
+  // entry e = 4 h + r is valid when r < n_roots[h]
+  const unsigned long long key = picp::block_winner<PNP_BS>(A.hyp * 4, cnt + ph0 * 4, s_key, [&](int e) {
+    return (e & 3) < n_roots[ph0 + (e >> 2)];
+  });
+  const int best = picp::winner_count(key);
   const bool ok = key != 0 && n >= 4 && best >= A.min_inliers;
-  const float* Tp = hyp_T + (ph0 * 4 + (unsigned)~(unsigned)key) * PNP_POSE;  // read only when ok
+  const float* Tp = hyp_T + (ph0 * 4 + picp::winner_entry(key)) * PNP_POSE;  // read only when ok
   if (tid < 16) {
     float val = (tid % 5 == 0) ? 1.0f : 0.0f;  // the identity, and the bottom row of a pose
     const int r = tid & 3, c = tid >> 2;
@@ -242,14 +189,6 @@ extern "C" __global__ __launch_bounds__(PNP_BS) void picp_pnp_select_kernel(
 // Every per-(problem, hypothesis) array is indexed p * hyp + h; problems sit on grid x.
 extern "C" int picp_pnp_score_tile(void) { return PNP_TILE; }
 extern "C" int picp_pnp_hyp_tile(void) { return PNP_HT; }
-
-extern "C" hipError_t picp_launch_pnp_samples(hipStream_t stream, const PnpArgs* A, const PnpItems* I,
-                                              int32_t* samples) {
-  const int64_t g = (int64_t)A->n_problems * A->hyp;
-  hipLaunchKernelGGL(picp_pnp_samples_kernel, dim3((unsigned)((g + PNP_BS - 1) / PNP_BS)), dim3(PNP_BS), 0, stream, *A,
-                     *I, samples);
-  return hipGetLastError();
-}
 
 extern "C" hipError_t picp_launch_pnp_solve(hipStream_t stream, const PnpArgs* A, const PnpItems* I,
                                             const int32_t* samples, int32_t* n_roots, float* hyp_T) {

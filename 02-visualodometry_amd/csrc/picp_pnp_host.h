@@ -5,11 +5,10 @@
 
 #include <stdint.h>
 
-#include <vector>
-
 #include "picp_c.h"
 #include "picp_host.h"
 #include "picp_internal.h"
+#include "picp_ransac_host.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -18,10 +17,7 @@
 struct PnpRun {
   PnpArgs A;
   PnpItems I;
-  int nb = 0;       // score blocks
-  int hsplit = 1;   // hypothesis slices of the score grid
-  DevBuf<int2> blk;
-  std::vector<int64_t> blk_offs;  // the offsets blk was built for
+  RansacGrid grid;  // kept between calls: picp_relocalize runs frames of one size again and again
   DevBuf<int32_t> samples, n_roots, cnt, inliers, found;
   DevBuf<float> hyp_T, T;
   DevBuf<uint8_t> mask;  // allocated when asked for

@@ -28,10 +28,7 @@ extern "C" void picp_refine_params_default(picp_refine_params* p) {
 extern "C" int picp_refine_create(picp_refine_t** out, int device, int rows, int cols, const float K[9]) {
   CHECK_ARG(out && K, "picp_refine_create: null argument");
   CHECK_ARG(rows > 0 && cols > 0, "picp_refine_create: rows/cols must be positive");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_refine_create: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = select_device("picp_refine_create", device)) return rc;
   picp_refine* h = new picp_refine();
   h->device = device;
   h->rows = rows;

@@ -1,6 +1,6 @@
 // picp_runtime.cpp -- what every part of the host runtime behind the C-ABI (include/picp_c.h)
-// shares: the thread's last error, the ABI version and parameter defaults, the device count, and
-// the helpers of picp_host.h.  The subsystems are in picp_batch.cpp (batch solver),
+// shares: the thread's last error, the ABI version and parameter defaults, the device count and
+// selection, and the helpers of picp_host.h.  The subsystems are in picp_batch.cpp (batch solver),
 // picp_batch_classify.cpp, picp_handle.cpp (single-problem handle), picp_frontend.cpp,
 // picp_refine_runtime.cpp, picp_vo_runtime.cpp and picp_comm.cpp.  No torch, no host fallback:
 // every compute entry point runs the HIP kernels or fails with PICP_ERR_DEVICE.
@@ -50,6 +50,14 @@ extern "C" int picp_device_count(int* n) {
   int c = 0;
   HIP_TRY(hipGetDeviceCount(&c));
   *n = c;
+  return PICP_OK;
+}
+
+int select_device(const char* what, int device) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return set_err(PICP_ERR_ARG, "%s: no such HIP device", what);
+  HIP_TRY(hipSetDevice(device));
   return PICP_OK;
 }
 

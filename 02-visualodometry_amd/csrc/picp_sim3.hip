@@ -1,8 +1,7 @@
 // picp_sim3.hip -- 3D-3D alignment robust to wrong matches: Umeyama's closed form inside RANSAC for
-// a ragged batch of matched point sets, with local optimisation.  The 3D-3D
-// sibling of picp_pnp.hip.  Five launches:
-//   1. picp_sim3_samples_kernel  one lane per (problem, hypothesis): three distinct indices, the
-//                                sampling function of include/picp_c.h;
+// a ragged batch of matched point sets, with local optimisation.  Five launches;
+// what the P3P solver has too is in picp_ransac.h:
+//   1. picp_ransac_samples_kernel (picp_ransac.hip): three distinct indices per (problem, hypothesis);
 //   2. picp_sim3_hyp_kernel      one lane per (problem, hypothesis), in double with contraction
 //                                off: the moments of the three pairs about the first, the closed
 //                                form (picp_umeyama.h), the transform rounded to float32;
@@ -23,6 +22,7 @@
 
 #include "picp_internal.h"
 #include "picp_launch.h"
+#include "picp_ransac.h"
 #include "picp_umeyama.h"
 #include "picp_wave.h"
 
@@ -35,30 +35,6 @@
 #define S3_T SIM3_XF              // floats of a stored transform: M = c R column-major, t, c, 3 unused
 
 namespace {
-
-// splitmix64's output function of the state x + golden gamma
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// the sampling function of include/picp_c.h (n >= 3); picp_pnp.hip has the same
-__device__ __forceinline__ void sample_triple(uint64_t seed, uint32_t i, uint32_t h, uint32_t n, int32_t id[3]) {
-  const uint64_t key = mix64(seed ^ mix64(((uint64_t)i << 32) | h));
-  const uint64_t r0 = mix64(key) >> 32, r1 = mix64(key + 1) >> 32, r2 = mix64(key + 2) >> 32;
-  const uint32_t a = (uint32_t)((r0 * n) >> 32);
-  uint32_t b = (uint32_t)((r1 * (n - 1)) >> 32);
-  b += (b >= a) ? 1u : 0u;
-  uint32_t c = (uint32_t)((r2 * (n - 2)) >> 32);
-  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  c += (c >= lo) ? 1u : 0u;
-  c += (c >= hi) ? 1u : 0u;
-  id[0] = (int32_t)a;
-  id[1] = (int32_t)b;
-  id[2] = (int32_t)c;
-}
 
 // the squared distance of M p + t from q in float32, in the order include/picp_c.h states
 __device__ __forceinline__ float sim3_d2(const float* S, float x, float y, float z, float qx, float qy, float qz) {
@@ -193,18 +169,6 @@ __device__ __forceinline__ bool fit_members(const Sim3Items& I, int64_t b, int n
 
 }  // namespace
 
-// 1. the samples of (problem, hypothesis) g = p * hyp + h
-extern "C" __global__ __launch_bounds__(S3_BS) void picp_sim3_samples_kernel(Sim3Args A, Sim3Items I,
-                                                                             int32_t* __restrict__ samples) {
-  const int64_t g = (int64_t)blockIdx.x * S3_BS + threadIdx.x;
-  if (g >= (int64_t)A.n_problems * A.hyp) return;
-  const int p = (int)(g / A.hyp), h = (int)(g % A.hyp);
-  const int64_t n = I.offs[p + 1] - I.offs[p];
-  int32_t id[3] = {0, 0, 0};
-  if (n >= 4) sample_triple(A.seed, (uint32_t)(A.prob0 + p), (uint32_t)h, (uint32_t)n, id);
-  for (int k = 0; k < 3; ++k) samples[3 * g + k] = id[k];
-}
-
 // 2. the transform of (problem, hypothesis) g
 extern "C" __global__ __launch_bounds__(64) void picp_sim3_hyp_kernel(Sim3Args A, Sim3Items I,
                                                                       const int32_t* __restrict__ samples,
@@ -290,26 +254,11 @@ extern "C" __global__ __launch_bounds__(S3_BS) void picp_sim3_select_kernel(Sim3
                                                                             const int32_t* __restrict__ cnt,
                                                                             int32_t* __restrict__ win) {
   __shared__ unsigned long long s_key[S3_BS / 64];
-  const int p = blockIdx.x, tid = threadIdx.x;
+  const int p = blockIdx.x;
   const size_t ph0 = (size_t)p * A.hyp;
-  // key of a valid hypothesis h: (count + 1) above ~h, so the maximum is the largest count at the
-  // lowest hypothesis and 0 means none; it does not depend on who finds it
-  unsigned long long key = 0;
-  for (int h = tid; h < A.hyp; h += S3_BS) {
-    if (!hyp_valid[ph0 + h]) continue;
-    const unsigned long long k = ((unsigned long long)((unsigned)cnt[ph0 + h] + 1u) << 32) | (unsigned)~(unsigned)h;
-    key = k > key ? k : key;
-  }
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = __shfl_xor(key, m);
-    key = o > key ? o : key;
-  }
-  if ((tid & 63) == 0) s_key[tid >> 6] = key;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < S3_BS / 64; ++w) key = s_key[w] > key ? s_key[w] : key;
-    win[p] = key ? (int32_t)(unsigned)~(unsigned)key : -1;
-  }
+  const unsigned long long key =
+      picp::block_winner<S3_BS>(A.hyp, cnt + ph0, s_key, [&](int h) { return hyp_valid[ph0 + h] != 0; });
+  if (threadIdx.x == 0) win[p] = key ? (int32_t)picp::winner_entry(key) : -1;
 }
 
 // 5. the refits of problem blockIdx.x and its result.  Candidate 0 is the winner's transform;
@@ -469,14 +418,6 @@ extern "C" __global__ __launch_bounds__(S3_BS) void picp_vo_align_pairs_kernel(
 // Every per-(problem, hypothesis) array is indexed p * hyp + h; problems sit on grid x.
 extern "C" int picp_sim3_score_tile(void) { return S3_TILE; }
 extern "C" int picp_sim3_hyp_tile(void) { return S3_HT; }
-
-extern "C" hipError_t picp_launch_sim3_samples(hipStream_t stream, const Sim3Args* A, const Sim3Items* I,
-                                               int32_t* samples) {
-  const int64_t g = (int64_t)A->n_problems * A->hyp;
-  hipLaunchKernelGGL(picp_sim3_samples_kernel, dim3((unsigned)((g + S3_BS - 1) / S3_BS)), dim3(S3_BS), 0, stream, *A,
-                     *I, samples);
-  return hipGetLastError();
-}
 
 extern "C" hipError_t picp_launch_sim3_hyp(hipStream_t stream, const Sim3Args* A, const Sim3Items* I,
                                            const int32_t* samples, int32_t* hyp_valid, float* hyp_S) {

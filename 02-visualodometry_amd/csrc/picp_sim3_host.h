@@ -8,6 +8,7 @@
 #include "picp_c.h"
 #include "picp_host.h"
 #include "picp_internal.h"
+#include "picp_ransac_host.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -16,9 +17,7 @@
 struct Sim3Run {
   Sim3Args A;
   Sim3Items I;
-  int nb = 0;       // score blocks
-  int hsplit = 1;   // hypothesis slices of the score grid
-  DevBuf<int2> blk;
+  RansacGrid grid;
   DevBuf<int32_t> samples, hyp_valid, cnt, win, inliers, found, refit_count;
   DevBuf<float> hyp_S, S, scale, rms, refit_S;
   DevBuf<uint8_t> mask;  // allocated when asked for

@@ -1,12 +1,12 @@
 // picp_sim3_runtime.cpp -- 3D-3D alignment by Sim(3) RANSAC (picp_sim3.hip): the run and the
-// stateless batch calls, which upload, launch and download like the other front-end entry points.
+// stateless batch calls, which upload, launch and download like the other front-end entry points
+// (the parts shared with the P3P: picp_ransac_host.h).
 #include <hip/hip_runtime.h>
 
-#include <math.h>
+#include <limits.h>
 #include <stdint.h>
 #include <string.h>
 
-#include <algorithm>
 #include <vector>
 
 #include "picp_c.h"
@@ -14,7 +14,6 @@
 #include "picp_launch.h"
 #include "picp_sim3_host.h"
 
-#define SIM3_MAX_HYP_PER_CALL (1 << 24)
 #define SIM3_XF 16  // floats of a stored transform (picp_umeyama.h)
 
 extern "C" void picp_sim3_params_default(picp_sim3_params* p) {
@@ -35,7 +34,7 @@ int sim3_args(Sim3Args* A, const picp_sim3_params* prm, int n_problems) {
   CHECK_ARG(!(P.threshold != P.threshold), "sim3: threshold is NaN");
   CHECK_ARG(P.hypotheses >= 1 && P.hypotheses <= 65536, "sim3: hypotheses out of range [1, 65536]");
   CHECK_ARG(P.refits >= 0 && P.refits <= 8, "sim3: refits out of range [0, 8]");
-  CHECK_ARG((int64_t)n_problems * P.hypotheses <= SIM3_MAX_HYP_PER_CALL, "sim3: more than 2^24 hypotheses in one call");
+  CHECK_ARG((int64_t)n_problems * P.hypotheses <= RANSAC_MAX_HYP, "sim3: more than 2^24 hypotheses in one call");
   memset(A, 0, sizeof(*A));
   A->threshold = P.threshold;
   A->with_scale = P.with_scale ? 1 : 0;
@@ -49,20 +48,10 @@ int sim3_args(Sim3Args* A, const picp_sim3_params* prm, int n_problems) {
 
 int sim3_prepare(Sim3Run* R, hipStream_t st, const int64_t* offs, bool want_mask, bool debug) {
   const int np = R->A.n_problems, H = R->A.hyp;
-  const int tile = picp_sim3_score_tile();
-  int64_t nb64 = 0;
-  for (int i = 0; i < np; ++i) {
-    CHECK_ARG(offs[i + 1] - offs[i] <= INT32_MAX - tile, "sim3: a problem has too many pairs");
-    nb64 += (offs[i + 1] - offs[i] + tile - 1) / tile;
-  }
-  CHECK_ARG(nb64 <= INT32_MAX / 4, "sim3: too many pairs in one call");
-  R->nb = (int)nb64;
-  // few blocks: the hypothesis tiles are dealt to slices of the grid's y so the chip fills
-  const int tiles = (H + picp_sim3_hyp_tile() - 1) / picp_sim3_hyp_tile();
-  R->hsplit = std::min(tiles, std::max(1, 1024 / std::max(R->nb, 1)));
+  int rc = ransac_grid_prepare(&R->grid, st, offs, np, H, picp_sim3_score_tile(), picp_sim3_hyp_tile(), "sim3",
+                               "pairs");
+  if (rc) return rc;
   const int64_t G = (int64_t)np * H;
-  int rc;
-  if ((rc = R->blk.grow(R->nb))) return rc;
   if ((rc = R->samples.grow(3 * G))) return rc;
   if ((rc = R->hyp_valid.grow(G))) return rc;
   if ((rc = R->cnt.grow(G))) return rc;
@@ -78,29 +67,23 @@ int sim3_prepare(Sim3Run* R, hipStream_t st, const int64_t* offs, bool want_mask
     if ((rc = R->refit_S.grow(SIM3_XF * (int64_t)np * R->A.refits))) return rc;
     if ((rc = R->refit_count.grow((int64_t)np * R->A.refits))) return rc;
   }
-  if (R->nb) {
-    std::vector<int2> blk((size_t)R->nb);
-    size_t k = 0;
-    for (int i = 0; i < np; ++i)
-      for (int64_t first = 0; first < offs[i + 1] - offs[i]; first += tile) blk[k++] = make_int2(i, (int)first);
-    HIP_TRY(hipMemcpyAsync(R->blk, blk.data(), blk.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));  // blk is a local
-  }
   return PICP_OK;
 }
 
 hipError_t sim3_enqueue(Sim3Run* R, hipStream_t st, TimedSpans* spans, int rep) {
   const int64_t G = (int64_t)R->A.n_problems * R->A.hyp;
+  const RansacGrid& g = R->grid;
   hipError_t e = hipSuccess;
   auto begin = [&](int s) { return spans ? spans[s].begin(rep, st) : hipSuccess; };
   auto end = [&](int s) { return spans ? spans[s].end(rep, st) : hipSuccess; };
   if ((e = begin(0)) != hipSuccess) return e;
-  if ((e = picp_launch_sim3_samples(st, &R->A, &R->I, R->samples)) != hipSuccess) return e;
+  e = picp_launch_ransac_samples(st, R->A.seed, R->A.prob0, R->A.n_problems, R->A.hyp, R->I.offs, R->samples);
+  if (e != hipSuccess) return e;
   if ((e = end(0)) != hipSuccess || (e = begin(1)) != hipSuccess) return e;
   if ((e = picp_launch_sim3_hyp(st, &R->A, &R->I, R->samples, R->hyp_valid, R->hyp_S)) != hipSuccess) return e;
   if ((e = end(1)) != hipSuccess || (e = begin(2)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(R->cnt, 0, (size_t)G * sizeof(int32_t), st)) != hipSuccess) return e;
-  if ((e = picp_launch_sim3_score(st, &R->A, &R->I, R->nb, R->blk, R->hsplit, R->hyp_valid, R->hyp_S, R->cnt)) !=
+  if ((e = picp_launch_sim3_score(st, &R->A, &R->I, g.nb, g.blk, g.hsplit, R->hyp_valid, R->hyp_S, R->cnt)) !=
       hipSuccess)
     return e;
   if ((e = end(2)) != hipSuccess || (e = begin(3)) != hipSuccess) return e;
@@ -114,44 +97,24 @@ hipError_t sim3_enqueue(Sim3Run* R, hipStream_t st, TimedSpans* spans, int rep) 
 
 namespace {
 
-// the packed inputs of a stateless call on the device
-struct Sim3Upload {
-  DevBuf<int64_t> offs;
-  DevBuf<float> src, dst;
-  DevBuf<uint8_t> mask;
-};
-
 int check_batch_args(int n_problems, const int64_t* offs, const float* src, const float* dst) {
   CHECK_ARG(n_problems >= 0, "picp_sim3_batch: negative problem count");
   CHECK_ARG(offs, "picp_sim3_batch: null argument");
-  CHECK_ARG(offs[0] == 0, "picp_sim3_batch: offsets must start at 0");
-  for (int i = 0; i < n_problems; ++i)
-    CHECK_ARG(offs[i + 1] >= offs[i] && offs[i + 1] - offs[i] <= INT32_MAX, "picp_sim3_batch: bad offsets");
-  CHECK_ARG(offs[n_problems] == 0 || (src && dst), "picp_sim3_batch: null points");
-  return PICP_OK;
+  return check_ragged_batch("picp_sim3_batch", n_problems, offs, src, dst);
 }
 
-int sim3_upload(Sim3Items* I, Sim3Upload* U, int device, int n_problems, const int64_t* offs, const float* src,
+// the device and the packed inputs on it (a: src, b: dst)
+int sim3_upload(Sim3Items* I, RansacUpload* U, int device, int n_problems, const int64_t* offs, const float* src,
                 const float* dst) {
-  int ndev = 0, rc;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_sim3_batch: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
-  const int64_t total = offs[n_problems];
-  if ((rc = U->offs.grow(n_problems + 1))) return rc;
-  if ((rc = U->src.grow(3 * total))) return rc;
-  if ((rc = U->dst.grow(3 * total))) return rc;
-  HIP_TRY(hipMemcpy(U->offs, offs, (size_t)(n_problems + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (total) {
-    HIP_TRY(hipMemcpy(U->src, src, (size_t)total * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(U->dst, dst, (size_t)total * 3 * sizeof(float), hipMemcpyHostToDevice));
-  }
-  *I = Sim3Items{U->src, U->src + 1, U->src + 2, U->dst, U->dst + 1, U->dst + 2, 3, 3, U->offs, U->offs};
+  int rc = select_device("picp_sim3_batch", device);
+  if (rc) return rc;
+  if ((rc = ransac_upload(U, n_problems, offs, src, 3, dst, 3))) return rc;
+  *I = Sim3Items{U->a, U->a + 1, U->a + 2, U->b, U->b + 1, U->b + 2, 3, 3, U->offs, U->offs};
   return PICP_OK;
 }
 
 // everything up to the launches: arguments, device, upload, buffers
-int sim3_setup(Sim3Run* R, Sim3Upload* U, int device, int n_problems, const int64_t* offs, const float* src,
+int sim3_setup(Sim3Run* R, RansacUpload* U, int device, int n_problems, const int64_t* offs, const float* src,
                const float* dst, const picp_sim3_params* prm, bool want_mask, bool debug) {
   int rc = sim3_args(&R->A, prm, n_problems);
   if (rc) return rc;
@@ -181,7 +144,7 @@ extern "C" int picp_sim3_batch_debug(int device, int n_problems, const int64_t* 
   int rc = check_batch_args(n_problems, offs, src, dst);
   if (rc) return rc;
   Sim3Run R;
-  Sim3Upload U;
+  RansacUpload U;
   if (n_problems == 0) return sim3_args(&R.A, prm, 0);
   const bool debug = refit_S || refit_count;
   if ((rc = sim3_setup(&R, &U, device, n_problems, offs, src, dst, prm, mask != nullptr, debug))) return rc;
@@ -230,18 +193,9 @@ extern "C" int picp_sim3_batch_time(int device, int n_problems, const int64_t* o
   int rc = check_batch_args(n_problems, offs, src, dst);
   if (rc) return rc;
   Sim3Run R;
-  Sim3Upload U;
+  RansacUpload U;
   if ((rc = sim3_setup(&R, &U, device, n_problems, offs, src, dst, prm, false, false))) return rc;
-  TimedSpans spans[5] = {TimedSpans(reps), TimedSpans(reps), TimedSpans(reps), TimedSpans(reps), TimedSpans(reps)};
-  for (TimedSpans& s : spans) HIP_TRY(s.create());
-  HIP_TRY(sim3_enqueue(&R, nullptr, nullptr, 0));  // untimed: first-launch costs
-  for (int r = 0; r < reps; ++r) HIP_TRY(sim3_enqueue(&R, nullptr, spans, r));
-  for (int s = 0; s < 5; ++s) {
-    double ms = 0.0;
-    HIP_TRY(spans[s].sum_ms(nullptr, &ms));
-    us[s] = (float)(1000.0 * ms / reps);
-  }
-  return PICP_OK;
+  return ransac_time_stages(5, reps, us, [&](TimedSpans* s, int r) { return sim3_enqueue(&R, nullptr, s, r); });
 }
 
 extern "C" int picp_sim3_fit_batch(int device, int n_problems, const int64_t* offs, const float* src,
@@ -259,17 +213,18 @@ extern "C" int picp_sim3_fit_batch(int device, int n_problems, const int64_t* of
   A.n_problems = n_problems;
   A.fit_only = 1;
   Sim3Items I;
-  Sim3Upload U;
+  RansacUpload U;
   if ((rc = sim3_upload(&I, &U, device, n_problems, offs, src, dst))) return rc;
   const size_t np = (size_t)n_problems, total = (size_t)offs[n_problems];
+  DevBuf<uint8_t> mask_d;
   if (mask && total) {
-    if ((rc = U.mask.grow((int64_t)total))) return rc;
-    HIP_TRY(hipMemcpy(U.mask, mask, total, hipMemcpyHostToDevice));
+    if ((rc = mask_d.grow((int64_t)total))) return rc;
+    HIP_TRY(hipMemcpy(mask_d, mask, total, hipMemcpyHostToDevice));
   }
   DevBuf<float> S, sc, rm;
   DevBuf<int32_t> fo;
   if ((rc = S.grow(16 * (int64_t)np)) || (rc = sc.grow(np)) || (rc = rm.grow(np)) || (rc = fo.grow(np))) return rc;
-  HIP_TRY(picp_launch_sim3_refit(nullptr, &A, &I, nullptr, nullptr, (mask && total) ? (const uint8_t*)U.mask : nullptr,
+  HIP_TRY(picp_launch_sim3_refit(nullptr, &A, &I, nullptr, nullptr, (mask && total) ? (const uint8_t*)mask_d : nullptr,
                                  nullptr, nullptr, S, sc, nullptr, fo, rm, nullptr));
   HIP_TRY(hipMemcpy(S_out, S, np * 16 * sizeof(float), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(found, fo, np * sizeof(int32_t), hipMemcpyDeviceToHost));

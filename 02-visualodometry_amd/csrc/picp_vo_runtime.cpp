@@ -131,10 +131,7 @@ extern "C" int picp_vo_create(picp_vo_t** out, int device, int rows, int cols, c
   CHECK_ARG(mx <= (1 << 30), "picp_vo_create: frame too large");
   const int64_t n_obs = frame_off[n_frames];
   CHECK_ARG(n_obs == 0 || (uv && desc), "picp_vo_create: null observation arrays");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  CHECK_ARG(device >= 0 && device < ndev, "picp_vo_create: no such HIP device");
-  HIP_TRY(hipSetDevice(device));
+  if (int rc = select_device("picp_vo_create", device)) return rc;
   picp_vo* h = new picp_vo();
   h->device = device;
   h->rows = rows;

@@ -196,6 +196,35 @@ def test_ties_go_to_the_lowest_hypothesis_then_root(native, oracle):
     assert _check_winner(native, e, p, native.K_REF, 9.0, min_inliers=65) is None and e["inliers"] == 64
 
 
+def test_counts_over_several_hypothesis_tiles_and_slices(native, oracle):
+    """The score stage's walk beyond one tile of hypotheses: two whole tiles and a tile of 2 (130
+    hypotheses with the kernel's tile of 64).  A: one problem of one correspondence more than a
+    score block holds (1025): two score blocks, the second with a single item, and three slices of
+    grid y, one tile each.  B: 400 problems of 5: 400 score blocks, two slices; slice 0 walks tiles
+    0 and 2, slice 1 takes tile 1 (tests/test_ransac_cpu.py holds the plan of both shapes to these
+    figures).  The tile sizes are the library's own."""
+    HT, TILE = native.lib().picp_pnp_hyp_tile(), native.lib().picp_pnp_score_tile()
+    H, K, thr = 2 * HT + 2, native.K_REF, 9.0
+    # no outliers, so that nearly every triple has a pose and the tile of 2 is not empty; the
+    # pixel noise spreads the counts
+    p = _problem(TILE + 1, 31, pixel_noise=0.5)
+    d = native.pnp_ransac_batch([p["xyz"]], [p["uv"]], threshold=thr, hypotheses=H, debug=True, want_mask=True)[0]
+    seen = _check_counts(oracle, d, p, K, thr)
+    assert seen >= 8 and (d["n_roots"][HT:2 * HT] > 0).any() and (d["n_roots"][2 * HT:] > 0).any()  # every tile has a pose
+    _check_winner(native, d, p, K, thr)
+    ps = [_problem(5, 100 + i, pixel_noise=0.5) for i in range(400)]
+    out = native.pnp_ransac_batch([q["xyz"] for q in ps], [q["uv"] for q in ps], threshold=thr, hypotheses=H,
+                                  debug=True, want_mask=True)
+    for i, d in enumerate(out):
+        assert d["hyp_count"].shape == (H, 4) and (d["hyp_count"] >= 0).all() and (d["hyp_count"] <= 5).all()
+        assert (d["hyp_count"][np.arange(4)[None, :] >= d["n_roots"][:, None]] == 0).all(), i
+    for i in (0, 199, 399):
+        np.testing.assert_array_equal(out[i]["samples"], R.samples(0, i, H, 5))
+        assert _check_counts(oracle, out[i], ps[i], K, thr) >= 3
+        assert (out[i]["n_roots"][HT:2 * HT] > 0).any() and (out[i]["n_roots"][2 * HT:] > 0).any()
+        _check_winner(native, out[i], ps[i], K, thr)
+
+
 # ---------------------------------------------------------------------------------------------
 # 5. end to end: a ragged batch, polished by the batch solver
 # ---------------------------------------------------------------------------------------------

@@ -178,6 +178,31 @@ def test_counts_winner_refits_and_result_on_a_ragged_batch(native, thr):
                 assert d["found"] and d["inliers"] >= sizes[i] // 2 - 4
 
 
+def test_counts_over_several_hypothesis_tiles_and_slices(native):
+    """The score stage's walk beyond one tile of hypotheses: two whole tiles and a tile of 2 (130
+    hypotheses with the kernel's tile of 64).  A: one problem of one pair more than a score block
+    holds (1025): two score blocks, three slices of grid y, one tile each.  B: 400 problems of 5:
+    400 score blocks, two slices; slice 0 walks tiles 0 and 2, slice 1 takes tile 1.  The tile
+    sizes are the library's own."""
+    HT, TILE = native.lib().picp_sim3_hyp_tile(), native.lib().picp_sim3_score_tile()
+    H, thr = 2 * HT + 2, 0.01
+    src, dst = _problem(TILE + 1, 80)
+    d = native.sim3_ransac_batch([src], [dst], threshold=thr, hypotheses=H, seed=4, refits=2, want_mask=True,
+                                 debug=True)[0]
+    _check_result(d, src, dst, thr, 4, 2)
+    assert d["hyp_valid"][:HT].any() and d["hyp_valid"][HT:2 * HT].any() and d["hyp_valid"][2 * HT:].any()
+    ps = [_problem(5, 300 + i, outlier_frac=0.2) for i in range(400)]
+    out = native.sim3_ransac_batch([p[0] for p in ps], [p[1] for p in ps], threshold=thr, hypotheses=H, seed=4,
+                                   refits=2, want_mask=True, debug=True)
+    for i, d in enumerate(out):
+        assert d["hyp_count"].shape == (H,) and (d["hyp_count"] >= 0).all() and (d["hyp_count"] <= 5).all()
+        assert (d["hyp_count"][d["hyp_valid"] == 0] == 0).all(), i
+    for i in (0, 199, 399):
+        np.testing.assert_array_equal(out[i]["samples"], R.samples(4, i, H, 5))
+        _check_result(out[i], ps[i][0], ps[i][1], thr, 4, 2)
+        assert out[i]["hyp_valid"][HT:2 * HT].any() and out[i]["hyp_valid"][2 * HT:].any()
+
+
 def test_min_inliers_and_no_refits(native):
     src, dst = _problem(64, 30)
     for kw in (dict(min_inliers=60), dict(refits=0), dict(refits=8), dict(min_inliers=0, hypotheses=1)):
