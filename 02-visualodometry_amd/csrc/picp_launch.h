@@ -9,6 +9,7 @@
 
 #include "picp_c.h"
 #include "picp_internal.h"
+#include "picp_pgo_graph.h"
 
 extern "C" {
 
@@ -135,6 +136,11 @@ hipError_t picp_launch_sim3_refit(hipStream_t stream, const Sim3Args* A, const S
                                   const float* hyp_S, const uint8_t* fit_mask, float* refit_S, int32_t* refit_count,
                                   float* S_out, float* scale, int32_t* inliers, int32_t* found, float* rms,
                                   uint8_t* mask);
+
+// ---- picp_pgo.hip
+// one workgroup per graph of graphs[n_run] (device): the whole pose-graph solve (picp_pgo_solve.h)
+hipError_t picp_launch_pgo(hipStream_t stream, int n_run, const PgoGraph* graphs, const PgoArrays* A,
+                           const PgoArgs* P);
 
 // the glue of picp_vo_align_segments: the match problems (segment s + 1's map against segment s's)
 // from the map counts, the accepted queries per problem, and the pairs (packed float3) in ascending

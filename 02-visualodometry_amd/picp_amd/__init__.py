@@ -60,6 +60,7 @@ EXPORTED = [
     "picp_pnp_params_default", "picp_pnp_batch", "picp_pnp_batch_debug", "picp_pnp_batch_time", "picp_relocalize",
     "picp_sim3_params_default", "picp_sim3_batch", "picp_sim3_batch_debug", "picp_sim3_batch_time", "picp_sim3_fit_batch",
     "picp_vo_align_segments",
+    "picp_pgo_params_default", "picp_pgo_batch", "picp_pgo_batch_time",
 ]
 # state of one correspondence at a pose (include/picp_c.h PICP_CORR_*)
 CORR_SKIPPED, CORR_INLIER, CORR_OUTLIER = 0, 1, 2
@@ -121,6 +122,15 @@ class Sim3Params(ctypes.Structure):
                 ("with_scale", ctypes.c_int32), ("refits", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("seed", ctypes.c_uint64)]
 
+
+class PgoParams(ctypes.Structure):
+    """picp_pgo_params (include/picp_c.h): the pose-graph solver's form, step count, damping and stop."""
+    _fields_ = [("with_scale", ctypes.c_int32), ("iterations", ctypes.c_int32), ("damping", ctypes.c_double),
+                ("eps", ctypes.c_double)]
+
+
+# picp_pgo_batch's per-graph status (include/picp_c.h PICP_PGO_*)
+PGO_OK, PGO_BAD_INPUT, PGO_BAD_EDGE, PGO_DISCONNECTED, PGO_NOT_PD, PGO_TOO_LARGE = range(6)
 
 _lib = None
 # picp_exchange_fn (include/picp_c.h): int (*)(void* user, const void* send, void* recv, size_t bytes)
@@ -260,6 +270,11 @@ def lib():
         "picp_sim3_batch_time": ([i, i, ctypes.POINTER(i64), fp, fp, ctypes.POINTER(Sim3Params), i, fp], i),
         "picp_sim3_fit_batch": ([i, i, ctypes.POINTER(i64), fp, fp, u8p, i, fp, fp, fp, i32p], i),
         "picp_vo_align_segments": ([vp, ctypes.POINTER(Sim3Params), fp, fp, i32p, i32p, ctypes.POINTER(i64)], i),
+        "picp_pgo_params_default": ([ctypes.POINTER(PgoParams)], None),
+        "picp_pgo_batch": ([i, i, ctypes.POINTER(i64), ctypes.POINTER(i64), fp, u8p, i32p, fp, fp,
+                            ctypes.POINTER(PgoParams), fp, dp, dp, dp, dp, i32p, i32p], i),
+        "picp_pgo_batch_time": ([i, i, ctypes.POINTER(i64), ctypes.POINTER(i64), fp, u8p, i32p, fp, fp,
+                                 ctypes.POINTER(PgoParams), i, fp], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -919,6 +934,83 @@ def sim3_ransac_time(src_list, dst_list, reps, threshold=0.01, hypotheses=256, w
     _check(lib().picp_sim3_batch_time(device, len(src_list), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                       _fptr(src), _fptr(dst), ctypes.byref(prm), reps, _fptr(us)))
     return tuple(float(x) for x in us)
+
+
+def default_pgo_params(**kw):
+    p = PgoParams()
+    lib().picp_pgo_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _pgo_pack(graphs):
+    """The ragged arrays of picp_pgo_batch from dicts with S (n, 4, 4), fixed (n,), edges (m, 2), Z (m, 4, 4)
+    and, in all of them or in none, weight (m,)."""
+    G = len(graphs)
+    node_off, edge_off = np.zeros(G + 1, np.int64), np.zeros(G + 1, np.int64)
+    S, fixed, idx, Z, w = [], [], [], [], []
+    has_w = [g.get("weight") is not None for g in graphs]
+    assert all(has_w) or not any(has_w), "weights in every graph or in none"
+    for k, g in enumerate(graphs):
+        s = np.asarray(g["S"], np.float32).reshape(-1, 4, 4)
+        e = np.asarray(g["edges"], np.int32).reshape(-1, 2)
+        z = np.asarray(g["Z"], np.float32).reshape(-1, 4, 4)
+        f = np.asarray(g["fixed"]).astype(np.uint8).reshape(-1)
+        assert len(f) == len(s) and len(z) == len(e)
+        node_off[k + 1], edge_off[k + 1] = node_off[k] + len(s), edge_off[k] + len(e)
+        S.append(np.transpose(s, (0, 2, 1)).reshape(-1))  # column-major
+        Z.append(np.transpose(z, (0, 2, 1)).reshape(-1))
+        fixed.append(f)
+        idx.append(e.reshape(-1))
+        if has_w[k]:
+            w.append(np.asarray(g["weight"], np.float32).reshape(-1))
+            assert len(w[-1]) == len(e)
+    cat = lambda L, t: np.ascontiguousarray(np.concatenate(L) if L else np.zeros(0, t), dtype=t)
+    return (node_off, edge_off, cat(S, np.float32), cat(fixed, np.uint8), cat(idx, np.int32), cat(Z, np.float32),
+            cat(w, np.float32) if G and all(has_w) else None)
+
+
+def _pgo_args(device, graphs, packed):
+    node_off, edge_off, S, fixed, idx, Z, w = packed
+    i64p, u8p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint8)
+    return [device, len(graphs), node_off.ctypes.data_as(i64p), edge_off.ctypes.data_as(i64p),
+            _fptr(S) if len(S) else None, fixed.ctypes.data_as(u8p) if len(fixed) else None,
+            _i32ptr(idx) if len(idx) else None, _fptr(Z) if len(Z) else None, _fptr(w) if w is not None and len(w) else None]
+
+
+def pose_graph_batch(graphs, with_scale=True, iterations=10, damping=0.0, eps=0.0, device=0):
+    """picp_pgo_batch: pose-graph optimisation over Sim(3) of many graphs.  Each graph is a dict with S
+    (n, 4, 4) [[c R, t], [0, 1]] mapping node k's frame into the common frame, fixed (n,), edges
+    (m, 2) local (i, j), Z (m, 4, 4) mapping node j's frame into node i's and optionally weight (m,).
+    Returns per graph a dict with S (n, 4, 4) float32, cost_initial, cost_final, grad_initial,
+    grad_final, steps and status (PGO_*); a graph whose status is not PGO_OK keeps its input S."""
+    G = len(graphs)
+    packed = _pgo_pack(graphs)
+    node_off = packed[0]
+    prm = PgoParams(1 if with_scale else 0, iterations, damping, eps)
+    So = np.zeros(16 * max(int(node_off[-1]), 1), np.float32)
+    fig = [np.zeros(max(G, 1), np.float64) for _ in range(4)]
+    steps, status = np.zeros(max(G, 1), np.int32), np.zeros(max(G, 1), np.int32)
+    dptr = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    _check(lib().picp_pgo_batch(*_pgo_args(device, graphs, packed), ctypes.byref(prm), _fptr(So), dptr(fig[0]),
+                                dptr(fig[1]), dptr(fig[2]), dptr(fig[3]), _i32ptr(steps), _i32ptr(status)))
+    out = []
+    for k in range(G):
+        s = So[16 * node_off[k]:16 * node_off[k + 1]].reshape(-1, 4, 4)
+        out.append({"S": np.transpose(s, (0, 2, 1)).copy(), "cost_initial": float(fig[0][k]),
+                    "cost_final": float(fig[1][k]), "grad_initial": float(fig[2][k]), "grad_final": float(fig[3][k]),
+                    "steps": int(steps[k]), "status": int(status[k])})
+    return out
+
+
+def pose_graph_time(graphs, reps, with_scale=True, iterations=10, damping=0.0, eps=0.0, device=0):
+    """picp_pgo_batch_time: mean device time in us of the solve's one launch."""
+    packed = _pgo_pack(graphs)
+    prm = PgoParams(1 if with_scale else 0, iterations, damping, eps)
+    us = np.zeros(1, np.float32)
+    _check(lib().picp_pgo_batch_time(*_pgo_args(device, graphs, packed), ctypes.byref(prm), reps, _fptr(us)))
+    return float(us[0])
 
 
 class VOSequence:

@@ -48,6 +48,22 @@ def chain_similarities(S_list):
     return out
 
 
+def segment_graph(S_list, extra=()):
+    """The pose graph of a segmented run for picp_amd.pose_graph_batch: nodes are the segments,
+    initialised by chain_similarities(S_list) with node 0 fixed; edge (s, s + 1) carries S_list[s]; every
+    (i, j, Z) of `extra` (Z maps segment j's frame into segment i's: a revisit, a second measurement)
+    is one more edge.  Returns dict(S, fixed, edges, Z) of float32 / uint8 / int32 arrays; weights are
+    the caller's to add (graph["weight"], one per edge in this order)."""
+    n = len(S_list) + 1
+    edges = [(s, s + 1) for s in range(n - 1)] + [(int(i), int(j)) for i, j, _ in extra]
+    Z = [np.asarray(S, np.float32) for S in S_list] + [np.asarray(z, np.float32) for _, _, z in extra]
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    return {"S": np.stack(chain_similarities(S_list)).astype(np.float32), "fixed": fixed,
+            "edges": np.asarray(edges, np.int32).reshape(-1, 2),
+            "Z": np.stack(Z).astype(np.float32) if Z else np.zeros((0, 4, 4), np.float32)}
+
+
 def _rot_angle(R):
     return float(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
 

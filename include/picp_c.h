@@ -712,6 +712,86 @@ int picp_sim3_fit_batch(int device, int n_problems, const int64_t* offs, const f
 int picp_vo_align_segments(picp_vo_t* h, const picp_sim3_params* prm, float* S_out, float* scale, int32_t* inliers,
                            int32_t* found, int64_t* n_pairs);
 
+/* ---------------- pose-graph optimisation over Sim(3) ---------------- */
+/* "Here are similarities measured between frames (or segments), more of them than a chain needs:
+ * where does every frame go?"  Nodes are similarities, edges are measured relative similarities,
+ * the result is the nonlinear least-squares placement that spreads the disagreement.
+ *
+ * The batch is ragged.  Graph g owns nodes [node_off[g], node_off[g+1]) and edges
+ * [edge_off[g], edge_off[g+1]); both offsets start at 0.  Node k carries S_k (16 floats,
+ * column-major 4x4 [[c R, t], [0, 1]], the layout of S_out of picp_sim3_batch), which maps node k's
+ * frame into the common frame, and a `fixed` byte.  Edge e carries the local node indices
+ * edge_idx[2 e] = i and edge_idx[2 e + 1] = j, a similarity Z_e (16 floats) that maps node j's
+ * frame into node i's (what picp_vo_align_segments returns for i = s, j = s + 1), and a weight
+ * w_e >= 0; weight NULL means 1.
+ *
+ * Canonical form: every input matrix is first replaced, in double, by its nearest similarity.
+ * With M its upper 3x3: c = cbrt(det M), R the orthogonal polar factor of M / c (Newton's iteration
+ * R <- (R + R^-T) / 2 to convergence), t the fourth column.
+ *
+ * Residual and cost: r_e = Log(Z_e^-1 S_i^-1 S_j) in R^7, ordered (upsilon, omega, sigma), Log the
+ * Sim(3) logarithm: the 4x4 matrix logarithm read as [[omega^ + sigma I, upsilon], [0, 0]].
+ * cost = 1/2 sum w_e r_e^T r_e.  with_scale = 0 gives the SE(3) form: c is 1 for every canonical
+ * input, sigma is dropped from residual and update, 6 unknowns per node.
+ *
+ * Update: S_k <- S_k Exp(delta_k) for the nodes that are not fixed; fixed nodes keep their input
+ * bits.  The Jacobians are the true ones: with E = Z^-1 S_i^-1 S_j and S_ij = S_i^-1 S_j,
+ * d r / d delta_j = J_r^-1(r) and d r / d delta_i = -J_r^-1(r) Ad(S_ij^-1), Ad(S) for S = (c, R, t)
+ * the 7x7 [[c R, t^ R, -t], [0, R, 0], [0, 0, 1]]; J_r^-1(r) is taken by seven central differences
+ * of Log(E Exp(+-h e_c)), h = 2^-17, in double.
+ *
+ * Method: Gauss-Newton, `damping` added to the diagonal of H = sum w J^T J; the step solves the
+ * normal equations exactly (a block skyline Cholesky in node order).  `iterations` steps are run;
+ * with eps > 0 the steps end after the first one whose cost c satisfies c_before - c < eps c_before.
+ * All state and arithmetic are double; the outputs are rounded to float32 once at the end.
+ *
+ * Outputs: S_out (16 floats per node); per graph the cost and the gradient's 2-norm at the inputs
+ * and at the result (double), the steps run and a status.  Every output pointer except S_out is
+ * nullable.  The same inputs give the same bits on every call, and a graph's outputs do not depend
+ * on the other graphs of the batch.
+ *
+ * Status, per graph (the other graphs still run); a graph whose status is not PICP_PGO_OK gets
+ * S_out = its inputs, bit for bit.  The first that applies:
+ *   PICP_PGO_BAD_INPUT     an S or Z with an entry that is not finite or det M <= 0 (or whose
+ *                          canonical form is not finite), a weight that is negative or not finite
+ *   PICP_PGO_BAD_EDGE      an edge with i = j or an index outside [0, n)
+ *   PICP_PGO_DISCONNECTED  a node that is not fixed and that no path of edges of positive weight
+ *                          joins to a fixed node (a graph without edges is exempt)
+ *   PICP_PGO_TOO_LARGE     the factor's envelope in node order (block row a starts at the lowest
+ *                          free neighbour of free node a) has more than PICP_PGO_MAX_BLOCKS blocks
+ *   PICP_PGO_NOT_PD        a diagonal block was not positive definite during a factorisation, or
+ *                          the cost stopped being finite
+ * A graph with no edge, or no node that is not fixed, succeeds with S_out = its inputs and 0 steps
+ * (its cost is still reported).  A graph has at most 2^24 nodes and 2^24 edges (PICP_ERR_ARG). */
+#define PICP_PGO_OK 0
+#define PICP_PGO_BAD_INPUT 1
+#define PICP_PGO_BAD_EDGE 2
+#define PICP_PGO_DISCONNECTED 3
+#define PICP_PGO_NOT_PD 4
+#define PICP_PGO_TOO_LARGE 5
+#define PICP_PGO_MAX_BLOCKS (1 << 18)
+
+typedef struct picp_pgo_params {
+  int32_t with_scale;  /* default 1; 0: SE(3) */
+  int32_t iterations;  /* Gauss-Newton steps, default 10, 0..1000 */
+  double damping;      /* added to H's diagonal, default 0, >= 0 */
+  double eps;          /* relative cost decrease that ends the steps, default 0: run every step */
+} picp_pgo_params;
+
+void picp_pgo_params_default(picp_pgo_params* p);
+
+/* prm NULL = picp_pgo_params_default.  n_graphs == 0 returns PICP_OK. */
+int picp_pgo_batch(int device, int n_graphs, const int64_t* node_off, const int64_t* edge_off, const float* S,
+                   const uint8_t* fixed, const int32_t* edge_idx, const float* Z, const float* weight,
+                   const picp_pgo_params* prm, float* S_out, double* cost_initial, double* cost_final,
+                   double* grad_initial, double* grad_final, int32_t* steps, int32_t* status);
+
+/* mean device time in us of the solve's one launch over `reps` repetitions after one untimed pass
+ * (device events; the plan and the upload are not timed); us[1] */
+int picp_pgo_batch_time(int device, int n_graphs, const int64_t* node_off, const int64_t* edge_off, const float* S,
+                        const uint8_t* fixed, const int32_t* edge_idx, const float* Z, const float* weight,
+                        const picp_pgo_params* prm, int reps, float* us);
+
 /* ---------------- self-test ---------------- */
 /* The projection's reciprocal 1/z must be the correctly rounded one (src/camera.h:30; the
  * chi2 gate is bit-exact): the kernels use a 3-instruction form, valid for every float in
