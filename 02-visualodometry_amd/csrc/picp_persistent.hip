@@ -13,8 +13,9 @@
 //      (deterministic: every solver gets the same bits), solve the damped 6x6 system and apply
 //      the update (picp_solve6.h: finish_round), then publish the new pose as 16 granules
 //      {round+1, word} twice: kept in their XCD's L2 and agent-scope;
-//   3. every other block polls its solver's 16 pose granules (one wave) -- the L2 copy once the
-//      first round has shown that it runs on the solver's XCD -- then starts the next round.
+//   3. every other block polls its solver's 16 pose granules (one wave: a ring of polls in
+//      flight, PICP_POSE_POLLS of them with one item per lane and two otherwise) -- the L2 copy
+//      once the first round has shown that it runs on the solver's XCD -- then starts the next round.
 // Correctness does not depend on placement or timing: only tags are trusted.  Blocks must be
 // co-resident (the host caps the grid at the CU count with ~110 VGPRs / 10 KB LDS per block),
 // every spin is bounded by a per-round s_memrealtime deadline (timeout -> error word, loop exits), and
@@ -35,8 +36,26 @@ typedef __attribute__((address_space(1))) unsigned int gu32_t;
 #define PICP_MAX_PBLK 256   // max blocks per problem in this mode (sweep registers)
 #define PICP_PBLOCK 512     // the partition's unit: npt items per lane of a 512-thread block
 // (npt 8 as 1024 threads x 4 items did not move C3: DESIGN.md Appendix A, "1024 x 4".)
-// Followers' pose wait: two polls in flight this many s_sleep units (64 clocks) apart
+// Followers' pose wait, two and more items per lane: two polls in flight this many s_sleep units
+// (64 clocks) apart
 #define PICP_POSE_STAGGER 8
+// Followers' pose wait, one item per lane: a ring of PICP_POSE_POLLS polls in flight, first issued
+// PICP_POSE_SPACING s_sleep units apart: one PICP_POSE_POLLS-th of the round trip of an sc1 load
+// served by the L2, which measures 80-120 ns (profiles/r16/pose_polls/pst_parent_c2.log).  Each is
+// re-issued as it is checked, so the spacing holds.  Two polls is the measured best: every poll
+// more in flight costs the round about 50 ns (the 24 followers of an XCD poll one L2 line, and the
+// solver's store and the poll that meets it queue behind them), one fewer 30 ns, and no spacing
+// from 2 to 8 units tells.  Both can be set from the make
+// line for A/B builds; 0 polls compiles the two-poll wait of the other kernels.
+#ifndef PICP_POSE_POLLS
+#define PICP_POSE_POLLS 2
+#endif
+#ifndef PICP_POSE_SPACING
+#define PICP_POSE_SPACING 2
+#endif
+static_assert(PICP_POSE_POLLS >= 0 && PICP_POSE_POLLS <= 16, "PICP_POSE_POLLS: 1 to 16 polls in flight, 0: the two-poll wait");
+// (The ring's first poll issued a lag after the block's post-linearize barrier, as the sweep's
+// first pass is: every lag from 200 ns on lost 1 %, DESIGN.md Appendix A "pose lag".)
 // The solvers' sweep with two passes in flight, PICP_SWEEP_STAGGER x 64 clocks apart.
 // Each pass loads every pending granule pair (the others point past the buffer's
 // range: no memory access, a zero), so both passes' loads are unconditional and the waits count
@@ -77,13 +96,22 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Diagnostic build only (-DPICP_STAMPS): s_memrealtime per phase of rounds (epochs) 11 and 12.
 #ifdef PICP_STAMPS
-__device__ unsigned long long picp_pstamps[2][256][8];
+// slots 0-7 as below; 8: a solver's pose stores issued (wave 0); a follower: 9, 10 one pose poll of
+// its own, issued and returned (the round trip of an sc1 load, taken right after the publish when
+// no pose can be there yet), 11: whether it polls the L2 copy (s_l2)
+#define PICP_PSTAMP_SLOTS 12
+__device__ unsigned long long picp_pstamps[2][256][PICP_PSTAMP_SLOTS];
 #define PSTAMP_T(k, t)                                                                         \
   do {                                                                                         \
     if (threadIdx.x == (t) && (epoch == 11 || epoch == 12) && blockIdx.x < 256)                \
       picp_pstamps[epoch - 11][blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();               \
   } while (0)
 #define PSTAMP(k) PSTAMP_T(k, 0)
+#define PSTAMP_VAL(k, val)                                                                     \
+  do {                                                                                         \
+    if (threadIdx.x == 0 && (epoch == 11 || epoch == 12) && blockIdx.x < 256)                  \
+      picp_pstamps[epoch - 11][blockIdx.x][k] = (val);                                         \
+  } while (0)
 // What a round waits for besides its hand-offs (slots 6 and 7).  A follower: thread 64 (wave 1,
 // which never polls) stamps the round start (6) and the pose barrier (7) beside wave 0's stamps
 // 0 and 2, so the stretch barrier -> next round start can be compared between the polling wave
@@ -274,6 +302,10 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
 
   float chi_prev = FLT_MAX;  // the leader's loop state besides the pose (exec/icp_test.cpp:89)
   unsigned long long pose_sink = 0, pa = 0, pb = 0;  // the follower's pose polls
+  // ... with one item per lane: the ring (pa and pb stay unused there)
+  constexpr bool RINGED = LANES && PICP_POSE_POLLS > 0;
+  constexpr int RING = RINGED ? PICP_POSE_POLLS : 1;
+  unsigned long long ring[RING] = {};
   for (unsigned epoch = 1; !s_done; ++epoch) {
     // every wait of this round is bounded from the round's start (a whole solve may take far
     // longer than timeout_ticks at large max_rounds; one round never does)
@@ -491,6 +523,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
               __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
             }
+            PSTAMP(8);
             if (lane < 13) s_ctl[lane] = cw;  // the pose and s_done (word 13, s_l2, is the follower's)
             if (o.done && leader) {
               if (lane < 12) ((unsigned*)(st_out + p))[lane] = cw;  // R (9), t (3): lane l owns word l
@@ -551,6 +584,7 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
               __hip_atomic_store(pose_l2 + lane, gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               __hip_atomic_store(pose_gl + lane, gw, RLX_AGENT);
             }
+            PSTAMP(8);
             if (lane == 0) {
 #pragma unroll
               for (int i = 0; i < 9; ++i) s_pose[i] = pr[i];
@@ -573,37 +607,96 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
       // path and does not merge with it at the bottom of the round: merged, the compiler copied
       // the in-flight poll's registers on the follower's back edge and waited for the poll first.
       pa = pb = pose_sink = 0;
+      if constexpr (RINGED) {
+#pragma unroll
+        for (int k = 0; k < RING; ++k) ring[k] = 0;
+      }
     } else {
       // ---- 3. wait for the leader's pose of this round (one wave, 16 lanes) ----
       if (wave == 0) {
         unsigned long long gp = 0;
-        // Two polls in flight, PICP_POSE_STAGGER x 64 clocks apart: each poll is re-issued as soon
-        // as it has been checked, so the pair keeps its offset and the pose is seen within about
-        // half a round trip of landing instead of a whole one (two polls issued together, checked
-        // in turn, measured no gain in round 2: they stay together).  Every lane loads (lanes >= 16
-        // repeat granule 15), so the waits count exactly one poll; the poll still in flight at the
-        // exit keeps its registers until the next round's wait consumes them (pose_sink), so
-        // nothing waits on it: pa, pb and pose_sink stay in the same registers round the loop
-        // (the solver path redefines them, above), the slice loads are retired before the loop,
-        // and last round's pair is folded into pose_sink before this round's first poll is issued
-        // (the empty asm pins the fold there: sunk below the spin, it would wait for the new poll).
-        // profiles/r11/waits/ has the back edge as compiled.
+        // Polls in flight, staggered when they are first issued (two, PICP_POSE_STAGGER x 64 clocks
+        // apart; with one item per lane the ring below): each poll is re-issued as soon as it has
+        // been checked, so they keep their offset.  Every lane loads (lanes >= 16 repeat granule
+        // 15), so a wait counts exactly one poll; the polls still in flight at the exit keep their
+        // registers until the next round's wait consumes them (pose_sink), so nothing waits on
+        // them: the poll state stays in the same registers round the loop (the solver path
+        // redefines it, above), the slice loads are retired before the loop, and last round's
+        // polls are folded into pose_sink before this round's first poll is issued (the empty asm
+        // pins the fold there: sunk below the spin, it would wait for the new poll).
+        // profiles/r11/waits/ and profiles/r16/pose_polls/ have the back edge as compiled.
         const int gl = lane < PICP_POSE_GRAN ? lane : PICP_POSE_GRAN - 1;
         // sc1 loads either way: past the L1, served by the L2 (the L2 copy's line stays there)
         const gu64_t* src = s_l2 ? pose_l2 : pose_gl;
         auto poll = [&]() -> unsigned long long { return __hip_atomic_load(src + gl, RLX_AGENT); };
         auto good = [&](unsigned long long v) { return __all((unsigned)(v >> 32) == tbase + epoch); };
-        pose_sink ^= pa ^ pb;  // last round's polls: long complete
-        asm volatile("" : "+v"(pose_sink));
+#ifdef PICP_STAMPS
+        if (epoch == 11 || epoch == 12) {  // one poll's round trip, where no pose can be there yet
+          PSTAMP_VAL(11, (unsigned long long)s_l2);
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the stamp's store is out of the way
+          const unsigned long long t_issue = __builtin_amdgcn_s_memrealtime();
+          asm volatile("" ::: "memory");
+          unsigned long long probe = poll();
+          asm volatile("" : "+v"(probe)::"memory");
+          __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the probe is back
+          asm volatile("" ::: "memory");
+          const unsigned long long t_back = __builtin_amdgcn_s_memrealtime();
+          PSTAMP_VAL(9, t_issue);
+          PSTAMP_VAL(10, t_back);
+        }
+#endif
         bool tmo = false;
-        pa = poll();
-        __builtin_amdgcn_s_sleep(PICP_POSE_STAGGER);
-        for (;;) {
-          pb = poll();
-          if (good(pa)) { gp = pa; break; }
+        if constexpr (RINGED) {
+          // The ring: PICP_POSE_POLLS polls in flight, PICP_POSE_SPACING x 64 clocks apart, so a
+          // pose that lands in the L2 is met by the next poll to arrive there, a PICP_POSE_POLLS-th
+          // of a round trip later at the most.  Polls return in the order they were issued, so
+          // checking the oldest waits for exactly that one; it is re-issued at once.  The deadline
+          // is read once per trip round the ring.
+          // Once the pose is found the trip's remaining checks (their waits) are skipped but not
+          // its remaining polls: issued on every path, they leave the registers in one order of
+          // ages (ring[0] oldest) however the trip ended.  As compiled, every way out of the loop
+          // meets its back edge in one block, and the compiler's wait for a check counts for the
+          // youngest age the register has on any path to it: with the polls inside the branches the
+          // trip's first check waited for all but one poll (s_waitcnt vmcnt(1) for
+          // vmcnt(PICP_POSE_POLLS - 1)) and the ring went out in bursts.  The extra polls cost an
+          // issue slot each and land unused.
+#pragma unroll
+          for (int k = 0; k < RING; ++k) pose_sink ^= ring[k];  // last round's polls: long complete
+          asm volatile("" : "+v"(pose_sink));
+#pragma unroll
+          for (int k = 0; k < RING; ++k) {
+            ring[k] = poll();
+            if (k < RING - 1) __builtin_amdgcn_s_sleep(PICP_POSE_SPACING);
+          }
+          for (;;) {
+            bool found = false;
+#pragma unroll
+            for (int k = 0; k < RING; ++k) {
+              if (!found) {
+                asm volatile("" : "+v"(ring[k]));  // the wait for this poll stays behind the test
+                if (good(ring[k])) {
+                  found = true;
+                  gp = ring[k];
+                }
+              }
+              ring[k] = poll();
+            }
+            if (found) break;
+            if (timed_out(deadline)) { tmo = true; break; }
+          }
+        } else {
+          pose_sink ^= pa ^ pb;  // last round's polls: long complete
+          asm volatile("" : "+v"(pose_sink));
           pa = poll();
-          if (good(pb)) { gp = pb; break; }
-          if (timed_out(deadline)) { tmo = true; break; }
+          __builtin_amdgcn_s_sleep(PICP_POSE_STAGGER);
+          for (;;) {
+            pb = poll();
+            if (good(pa)) { gp = pa; break; }
+            pa = poll();
+            if (good(pb)) { gp = pb; break; }
+            if (timed_out(deadline)) { tmo = true; break; }
+          }
         }
         if (tmo) {
           if (lane == 0) __hip_atomic_store(errw, 2u, RLX_AGENT);
@@ -621,7 +714,14 @@ __global__ __launch_bounds__(BS) void picp_persistent_kernel(
     }
   }
   // an opaque never-true test keeps the follower's last in-flight poll alive to here
-  if (timeout_ticks == ~0ull && (pose_sink ^ pa ^ pb) == 1ull) s_pose[0] = 0.0f;
+  if constexpr (RINGED) {
+    unsigned long long left = pose_sink;
+#pragma unroll
+    for (int k = 0; k < RING; ++k) left ^= ring[k];
+    if (timeout_ticks == ~0ull && left == 1ull) s_pose[0] = 0.0f;
+  } else {
+    if (timeout_ticks == ~0ull && (pose_sink ^ pa ^ pb) == 1ull) s_pose[0] = 0.0f;
+  }
 }
 
 #ifdef PICP_STAMPS

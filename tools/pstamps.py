@@ -4,7 +4,11 @@ Stamps: 0 round start, 1 partial published, 2 leader: sweep done / others: pose 
 3 leader: solve done; the sweep passes (issue, return) of each of the leader's 8 waves (its first lane still sweeping),
 with the wave's post-linearize barrier and pass count; and what a round waits
 for besides its hand-offs (6, 7): in a follower, wave 1's round start and pose barrier beside the
-polling wave's (0, 2); in a solver, the sweep's exit and the end of the double sums."""
+polling wave's (0, 2); in a solver, the sweep's exit and the end of the double sums.
+Slot 8 is a solver's pose stores (wave 0), so a follower's detection delay is its pose barrier (2)
+less its solver's slot 8; slots 9 and 10 are one pose poll of the follower, issued and returned
+right after its publish (the round trip of an sc1 load when no pose can be there yet), and slot 11
+says whether it polls the L2 copy of the pose."""
 import argparse
 import ctypes
 import os
@@ -13,6 +17,39 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "02-visualodometry_amd"))
 os.environ["PICP_LIB"] = os.environ.get("PICP_STAMPS_LIB") or os.path.join(ROOT, "02-visualodometry_amd", "lib", "libpicp_amd_stamps.so")
+
+
+def hist40(x):
+    """Counts in 40 ns steps (the stamps' own step), as 'from:count' pairs."""
+    import numpy as np
+    b = (np.asarray(x) // 40) * 40
+    return " ".join("%d:%d" % (v, int((b == v).sum())) for v in sorted(set(b.tolist())))
+
+
+def pose_fanout(st, ns, nb):
+    """Solver pose stores (slot 8) -> each follower's pose barrier (slot 2), by solver; the
+    followers' own poll round trip (slots 9, 10) and which pose copy they poll (slot 11)."""
+    import numpy as np
+    kb = np.arange(ns, nb)
+    delay = (st[kb, 2] - st[kb % ns, 8]) * 10
+    print("  pose stored -> follower pose barrier (%d followers): min %d median %d max %d, spread %d ns" % (
+        len(kb), delay.min(), np.median(delay), delay.max(), delay.max() - delay.min()))
+    print("    histogram (ns:followers): %s" % hist40(delay))
+    for g in range(ns):
+        d = delay[kb % ns == g]
+        if len(d):
+            print("    solver %d (%2d followers): min %d median %d max %d  %s" % (g, len(d), d.min(), np.median(d), d.max(), hist40(d)))
+    first = (st[:ns, 8].min() - st[:, 0].min()) * 10
+    last_f = (st[kb, 2].max() - st[:, 0].min()) * 10
+    print("    first pose store at %d, last at %d, last follower barrier at %d (ns from the first round start)" % (
+        first, (st[:ns, 8].max() - st[:, 0].min()) * 10, last_f))
+    rtt = (st[kb, 10] - st[kb, 9]) * 10
+    print("  follower poll round trip (issue -> returned, right after the publish): min %d median %d max %d  %s" % (
+        rtt.min(), np.median(rtt), rtt.max(), hist40(rtt)))
+    l2 = st[kb, 11]
+    print("  followers polling the L2 copy: %d, the agent-scope copy: %d%s" % (
+        int((l2 != 0).sum()), int((l2 == 0).sum()),
+        "" if (l2 != 0).all() else "  (agent-scope: blocks %s, delays %s)" % (kb[l2 == 0].tolist(), delay[l2 == 0].tolist())))
 
 
 def main():
@@ -38,7 +75,7 @@ def main():
     assert L.picp_debug_sweepstamps(sw.ctypes.data, sw.size) == 0
     nb = info["n_blocks"]
     L.picp_debug_pstamps.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    buf = np.zeros((2, 256, 8), np.uint64)
+    buf = np.zeros((2, 256, 12), np.uint64)  # round, block, slot (picp_persistent.hip picp_pstamps)
     assert L.picp_debug_pstamps(buf.ctypes.data, buf.size) == 0
     for r in (0, 1):
         st = buf[r, :nb].astype(np.int64)
@@ -69,6 +106,8 @@ def main():
             pub = (buf[1, ns:nb, 1].astype(np.int64) - buf[0, ns:nb, 2].astype(np.int64)) * 10
             print("  followers pose barrier r11 -> published r12: median %d (min %d max %d)" % (
                 np.median(pub), pub.min(), pub.max()))
+        if nb > ns:
+            pose_fanout(st, ns, nb)
         last_pub = int(rel[:, 1].max())
         # the leader's sweep passes of every wave: issue -> loads returned, ns from the round
         # start (slot 62: the wave's post-linearize barrier, 63: its pass count)
